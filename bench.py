@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the PSIS-LOO hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--obs N_PER_GPU] [--draws S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--obs N_PER_GPU] [--draws S] [--dump-outputs DIR] [--full]
 
 A "step" is one fused pass (``pla_psis_loo``: smoothing + loo_i + lppd_i + reductions, plus the
 single all-reduce when N > 1) over one device-resident synthetic log-likelihood matrix.  The
@@ -9,10 +9,16 @@ default workload is BASELINE.json config C3 -- fp64, S=4000 draws x 1,000,000 ob
 GPU (32 GB), reff=1 -- the configuration the north-star target is quoted on.  Observations are
 sharded over ranks (weak scaling: every GPU holds 1e6 rows); ``value`` is whole-job obs/s.
 
-One JSON line is printed by rank 0; it also carries
+One JSON line is printed by rank 0.  A plain run only sets up, warms up, times the steps and prints it;
+with ``--full`` the line also carries what takes measurements or runs of its own:
   roofline      algorithmic bytes (8*S + 24 per observation) / mean kernel time, against 8 TB/s
+                (HIP events bracket the launches of the timed steps)
   cpu_baseline  the NumPy oracle (the reference's per-observation loop restated) on a bounded
                 sample of the same matrix, one core; the same sample is the parity check.
+
+``--dump-outputs DIR`` writes what the last timed step returned (rank 0's shard) as float64 ``DIR/<name>.npy``:
+``diag`` (khat), ``loo_i``, ``lppd_i`` and the aggregates ``agg``.  The inputs are generated from the seed, so
+two builds can be compared output for output.
 """
 
 import argparse
@@ -25,6 +31,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 0x5EED00D0  # rows kept when the pointwise outputs exceed the limit: the same ones in every run
 
 
 def measured_traffic(n_obs, n_draws, dtype):
@@ -66,6 +74,28 @@ def rccl_version(torch):
         return ".".join(str(x) for x in v) if isinstance(v, (tuple, list)) else str(v)
     except Exception:  # (a record field: never worth failing the run for)
         return None
+
+
+def dump_outputs(out_dir, res):
+    """Write the last timed step's outputs as float64 .npy files.  The pointwise arrays are cut to a fixed, seeded sample
+    of rows (indices in ``rows.npy``) when all of them would exceed DUMP_LIMIT_BYTES."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    pointwise = {k: res[k] for k in ("diag", "loo_i", "lppd_i") if res.get(k) is not None}
+    arrays = {"agg": res["agg"]}
+    n = next(iter(pointwise.values())).numel() if pointwise else 0
+    cap = (DUMP_LIMIT_BYTES - 4096) // (8 * (len(pointwise) + 1))  # (+1: the row indices of a sample)
+    if n > cap:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=cap, replace=False))
+        idx = torch.from_numpy(rows).to(next(iter(pointwise.values())).device)
+        pointwise = {k: v.index_select(0, idx) for k, v in pointwise.items()}
+        arrays["rows"] = rows
+    arrays.update(pointwise)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64, copy=False))
 
 
 def launch_ranks(n):
@@ -127,8 +157,8 @@ def main():
     ap.add_argument("--draws", type=int, default=4000)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0003)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and parity leg")
     ap.add_argument("--layout", default="draws", choices=["draws", "obs"],
                     help="which index of the matrix is contiguous: the draws of an observation (default, BASELINE's C3) or the "
                          "observations of a draw -- ArviZ's (chain, draw, *obs) as pl.loo(idata) stacks it (loo.py:189), read in place")
@@ -139,7 +169,14 @@ def main():
     ap.add_argument("--config", default=None, choices=["C2", "C3", "C4", "C5"],
                     help="BASELINE.json preset (per-GPU shard): C2 = 1e5 x 4000 f64, C3 / C4 = 1e6 x 4000 f64 per GPU, "
                          "C5 = 125 000 x 20 000 f32 per GPU with 30 %% heavy-tailed rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) as float64 DIR/<name>.npy, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (kernel times from HIP events in the timed steps), the per-rank kernel times, "
+                         "the CPU baselines and the parity check against the oracle")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     label, heavy, k_hi = resolve_workload(args)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -200,9 +237,10 @@ def main():
             # the single collective.  RCCL: pack kernel + all-reduce of the preallocated world x 8 table + merge kernel, all on
             # the device, nothing allocated, no host sync (gloo rehearsals: the same table through host memory)
             if backend == "nccl":
-                return all_reduce_aggregates_device(res["agg"], eng)
-            return all_reduce_aggregates(res["agg"], as_tensor=True)
-        return res["agg"]
+                res["agg"] = all_reduce_aggregates_device(res["agg"], eng)
+            else:
+                res["agg"] = all_reduce_aggregates(res["agg"], as_tensor=True)
+        return res
 
     def fence():
         torch.cuda.synchronize()
@@ -213,33 +251,40 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # hipEvents bracket every launch of the row kernels on the launch stream, inside the timed region
+    # --full: hipEvents bracket every launch of the row kernels on the launch stream, inside the timed region
     # (recorded into a ring and read back after the loop: the host never waits in between)
-    eng.set_timing(True)
+    eng.set_timing(args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        agg = step()
+        last = None  # (the previous step's buffers return to the allocator first: every step reuses the same blocks)
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
-    k_ms, k_n = eng.kernel_ms()
-    f_ms, f_n = eng.first_kernel_ms()
-    eng.set_timing(False)
+    if args.full:
+        k_ms, k_n = eng.kernel_ms()
+        f_ms, f_n = eng.first_kernel_ms()
+        eng.set_timing(False)
     gave_up = eng.stream_gave_up()  # streamed passes in which the fit kernel stopped waiting for the sweep (0 in a healthy run)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    agg = last["agg"]
     agg = agg.cpu().numpy() if hasattr(agg, "cpu") else np.asarray(agg)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
-    # ---- roofline of the LOO pass: wave kernel (selection) + fit kernel + the rows handed to the general kernel,
-    #      timed together with HIP events on the launch stream
-    kernel_ms = k_ms / max(args.steps, 1)  # per PASS (a pass over more than 2^20 rows is several bracketed launches)
-    alg_bytes = n_local * (S * esz + 24.0)
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-    kernels_text = eng.last_kernels()
+    if args.full:
+        # ---- roofline of the LOO pass: wave kernel (selection) + fit kernel + the rows handed to the general kernel,
+        #      timed together with HIP events on the launch stream
+        kernel_ms = k_ms / args.steps  # per PASS (a pass over more than 2^20 rows is several bracketed launches)
+        alg_bytes = n_local * (S * esz + 24.0)
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+        kernels_text = eng.last_kernels()
     per_rank = None
     if world > 1:
-        mine = {"rank": rank, "device": dev_index, "name": torch.cuda.get_device_name(dev_index), "kernel_ms": kernel_ms}
+        mine = {"rank": rank, "device": dev_index, "name": torch.cuda.get_device_name(dev_index),
+                "kernel_ms": kernel_ms if args.full else None}
         per_rank = [None] * world
         try:
             dist.all_gather_object(per_rank, mine)
@@ -252,9 +297,6 @@ def main():
             dist.destroy_process_group()
         return
 
-    traffic, traffic_file = measured_traffic(n_local, S, args.dtype)
-    if args.layout == "obs":  # (the committed counts are of the draws-fastest pass; this layout's: profiles/r03_col_traffic.txt, per block)
-        traffic, traffic_file = None, None
     out = {
         "metric": "psis_loo_observations_per_second",
         "value": world * n_local * args.steps / elapsed,
@@ -264,7 +306,8 @@ def main():
         "backend": (backend if world > 1 else None),
         "rccl_version": rccl_version(torch) if world > 1 and backend == "nccl" else None,
         "devices_seen": ([r["device"] for r in per_rank] if per_rank else [dev_index]),
-        "kernel_ms_per_rank": ({"min": min(r["kernel_ms"] for r in per_rank), "max": max(r["kernel_ms"] for r in per_rank)} if per_rank else None),
+        "kernel_ms_per_rank": ({"min": min(r["kernel_ms"] for r in per_rank), "max": max(r["kernel_ms"] for r in per_rank)}
+                               if per_rank and args.full else None),
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
@@ -288,7 +331,12 @@ def main():
             "n_high_k": int(agg[4]),
             "rows_left_to_general_kernel": int(agg[7]),
         },
-        "roofline": {
+    }
+    if args.full:
+        traffic, traffic_file = measured_traffic(n_local, S, args.dtype)
+        if args.layout == "obs":  # (the committed counts are of the draws-fastest pass; this layout's: profiles/r03_col_traffic.txt, per block)
+            traffic, traffic_file = None, None
+        out["roofline"] = {
             "bound": "hbm",
             "achieved": achieved,
             "peak": HBM_PEAK_GBS,
@@ -300,18 +348,16 @@ def main():
             "kernel_ms": kernel_ms,
             "algorithmic_bytes_per_launch": alg_bytes,
             "kernels": "whole pass, one event pair on the caller's stream around: " + kernels_text,
-        },
-    }
-
-    if f_n:
-        # the dominant kernel alone (it reads the whole matrix; the fit kernel only sees the <= 250 tail values per observation)
-        first_ms = f_ms / f_n
-        out["roofline"]["dominant_kernel"] = {
-            "name": kernels_text.split("<")[0].split(" ")[0], "kernel_ms": first_ms, "achieved": alg_bytes / (first_ms * 1e-3) / 1e9,
-            "frac": alg_bytes / (first_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
         }
+        if f_n:
+            # the dominant kernel alone (it reads the whole matrix; the fit kernel only sees the <= 250 tail values per observation)
+            first_ms = f_ms / f_n
+            out["roofline"]["dominant_kernel"] = {
+                "name": kernels_text.split("<")[0].split(" ")[0], "kernel_ms": first_ms, "achieved": alg_bytes / (first_ms * 1e-3) / 1e9,
+                "frac": alg_bytes / (first_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            }
 
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         # ---- CPU baseline + parity on a bounded sample of the same matrix (one GPU only: at N > 1 the other ranks would wait
         #      at the closing barrier for it, and the baseline is the same number) -------
         from oracle import psis_oracle as orc

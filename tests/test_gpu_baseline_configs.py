@@ -259,7 +259,7 @@ def test_bench_launches_two_ranks(eng):
     import torch
 
     n_local, S = 20000, 4000
-    out = _run_bench(["--gpus", "2", "--obs", str(n_local), "--steps", "2", "--warmup", "1", "--no-cpu"],
+    out = _run_bench(["--gpus", "2", "--obs", str(n_local), "--steps", "2", "--warmup", "1", "--no-cpu", "--full"],
                      {"PYLOO_AMD_BENCH_BACKEND": "gloo", "PYLOO_AMD_BENCH_DEVICE": "0"})
     assert out["n_gpus"] == 2 and out["ranks"] == 2 and out["backend"] == "gloo" and out["scaling"] == "weak"
     assert out["devices_seen"] == [0, 0] and out["kernel_ms_per_rank"]["min"] <= out["kernel_ms_per_rank"]["max"]
@@ -280,7 +280,7 @@ def test_bench_launches_four_ranks(eng):
     import torch
 
     n_local, S = 4000, 4000
-    out = _run_bench(["--gpus", "4", "--obs", str(n_local), "--steps", "2", "--warmup", "1", "--no-cpu"],
+    out = _run_bench(["--gpus", "4", "--obs", str(n_local), "--steps", "2", "--warmup", "1", "--no-cpu", "--full"],
                      {"PYLOO_AMD_BENCH_BACKEND": "gloo", "PYLOO_AMD_BENCH_DEVICE": "0"})
     assert out["n_gpus"] == 4 and out["ranks"] == 4 and out["backend"] == "gloo" and out["scaling"] == "weak"
     assert out["devices_seen"] == [0, 0, 0, 0] and out["kernel_ms_per_rank"]["min"] <= out["kernel_ms_per_rank"]["max"]
@@ -293,6 +293,26 @@ def test_bench_launches_four_ranks(eng):
     agg = eng.psis_loo(t, 190, "psis", 1.0, 0.7, pointwise=False)["agg"].cpu().numpy()
     np.testing.assert_allclose(out["config"]["elpd_loo"], agg[1], rtol=1e-12)
     assert out["config"]["n_high_k"] == agg[4]
+
+
+def test_plain_bench_run_and_its_output_dump(eng, tmp_path):
+    """A plain `python bench.py` line (no --full): the headline fields only, the number of timed steps asked for, and
+    --dump-outputs writing what the last timed step returned -- the pass over the same seeded matrix, run here directly."""
+    import torch
+
+    n_local, S = 20000, 4000
+    out = _run_bench(["--obs", str(n_local), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], {})
+    assert (out["metric"], out["unit"], out["higher_is_better"], out["dtype"]) == ("psis_loo_observations_per_second", "obs/s", True, "f64")
+    assert out["steps"] == 3 and abs(out["value"] - n_local * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+    assert not {"roofline", "cpu_baseline", "parity", "cpu_baseline_vectorised"} & set(out) and out["kernel_ms_per_rank"] is None
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("diag", "loo_i", "lppd_i", "agg")}
+    assert all(a.dtype == np.float64 for a in got.values()) and not (tmp_path / "rows.npy").exists()
+    t = torch.empty((n_local, S), dtype=torch.float64, device="cuda")
+    eng.fill_synthetic(t, seed=0x5EED0003)
+    want = eng.psis_loo(t, 190, "psis", 1.0, 0.7, pointwise=False)
+    for k, a in got.items():
+        np.testing.assert_allclose(a, want[k].cpu().numpy(), rtol=1e-12, err_msg=k)
+    np.testing.assert_allclose(out["config"]["elpd_loo"], got["agg"][1], rtol=1e-15)
 
 
 def test_rccl_all_reduce_world_size_one():

@@ -218,3 +218,31 @@ def test_device_side_merge_kernel_contract():
     lib = _capi.load_library()
     assert lib.pla_aggregate_pack(None, None, 0, 1, None, None) < 0  # argument errors are status codes
     assert lib.pla_aggregate_merge(None, None, 0, None, None) < 0
+
+
+def test_bench_output_dump_keeps_under_its_limit(tmp_path):
+    """`bench.py --dump-outputs`: float64 files; pointwise outputs too large for the limit are cut to the same seeded sample
+    of rows in every array (indices in rows.npy), small ones are written whole."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_under_test3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for n in (1000, 3_000_000):
+        res = {k: torch.arange(n, dtype=torch.float64) * (i + 1) for i, k in enumerate(("diag", "loo_i", "lppd_i"))}
+        res["agg"] = torch.arange(8, dtype=torch.float64)
+        d = tmp_path / str(n)
+        bench.dump_outputs(str(d), res)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_LIMIT_BYTES
+        got = {f.stem: np.load(f) for f in d.iterdir()}
+        assert all(a.dtype == np.float64 for a in got.values())
+        np.testing.assert_array_equal(got["agg"], np.arange(8))
+        rows = got.get("rows", np.arange(n, dtype=np.float64))
+        assert ("rows" in got) == (n > 1000) and len(rows) == len(np.unique(rows))
+        for i, k in enumerate(("diag", "loo_i", "lppd_i")):
+            np.testing.assert_array_equal(got[k], rows * (i + 1))
+        if n > 1000:
+            bench.dump_outputs(str(tmp_path / "again"), res)
+            np.testing.assert_array_equal(np.load(tmp_path / "again" / "rows.npy"), rows)

@@ -9,5 +9,5 @@ if [ ! -f "$LIB" ] || [ "$ROOT/pyloo_amd/csrc/pla_wave.h" -nt "$LIB" ]; then
   (cd "$ROOT" && python -m pyloo_amd.build --alt=ablate -DPLA_WAVE_ABLATE=1 -DPLA_EXPERIMENT)
 fi
 for sk in "$@"; do
-  echo "skip=$sk"; PYLOO_AMD_LIB=$LIB PLA_DEBUG_SKIP=$sk timeout -k 10 120 python "$ROOT/bench.py" --obs ${OBS:-200000} --steps 5 --warmup 2 --no-cpu | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  kernel_ms', round(d['roofline']['kernel_ms'],3), 'GB/s', round(d['roofline']['achieved'],1))"
+  echo "skip=$sk"; PYLOO_AMD_LIB=$LIB PLA_DEBUG_SKIP=$sk timeout -k 10 120 python "$ROOT/bench.py" --obs ${OBS:-200000} --steps 5 --warmup 2 --full --no-cpu | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  kernel_ms', round(d['roofline']['kernel_ms'],3), 'GB/s', round(d['roofline']['achieved'],1))"
 done
