@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PLA_ABI_VERSION 4
+#define PLA_ABI_VERSION 5
 
 /* status codes */
 #define PLA_OK 0
@@ -180,6 +180,41 @@ int pla_waic_rows(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int
                   int64_t stride_obs, int64_t stride_draw, const int64_t *row_index, int64_t n_rows,
                   double scale_value, int mem_space, void *stream, double *lppd_i, double *var_i,
                   double *waic_i, double *agg);
+
+/*
+ * pla_group_sum / pla_psis_loo_groups -- leave-one-group-out (loo_group.py:216-300): the (n_obs, n_draws) matrix is reduced to
+ * one row per group, the sums of its members' rows, and the PSIS / SIS / TIS pass of pla_psis_loo runs over those G rows.
+ *
+ *   ll, n_obs, n_draws, strides   the matrix, as in pla_psis_loo (draws contiguous is read in place; observations contiguous is
+ *                 transposed block by block on the device; other strides: PLA_ERR_UNSUPPORTED)
+ *   group_offsets [n_groups + 1], group_members [group_offsets[n_groups]]  int64, in the memory space of `ll`: the members of
+ *                 group g are group_members[group_offsets[g] .. group_offsets[g+1]), observation indices in ascending order.  The
+ *                 groups need not cover every observation.  Host lists are checked (offsets start at 0 and never decrease,
+ *                 members in [0, n_obs) and ascending within a group: PLA_ERR_ARG); device lists are clamped into range on the
+ *                 device, as pla_psis_loo_rows does -- validate them before uploading.
+ *   group sums    out[g, s] = ll[m0, s] + ll[m1, s] + ... over the members in ascending order, one rounding per add, in the dtype of
+ *                 ll (f32 sums stay f32): bitwise NumPy's `ll[members].sum(axis=0)` (loo_group.py:221).  NaN entries count as -1e10
+ *                 (loo_group.py:188-197) and are counted in *n_replaced (memory space of ll; may be NULL); +-inf are not replaced.
+ *   pla_group_sum        out (n_groups, n_draws) C-contiguous, dtype of ll, in the memory space of ll
+ *   pla_psis_loo_groups  diag / logo_i / lppd_i [n_groups] double (each may be NULL), agg [PLA_AGG_COUNT] as pla_psis_loo's, reduced
+ *                 over the groups (n_groups >= 1).  The sums are built one block of groups at a time in a bounded engine buffer
+ *                 (sized like the ingest staging: PLA_INGEST_BLOCK_MB on the device), each block's pass writes its slices,
+ *                 the aggregates are reduced once at the end: the results do not depend on the block size.  A host matrix, or an
+ *                 observations-fastest one, whose group sums fill more than one block is read once per block.
+ */
+/* sums of the rows of each group (loo_group.py:216-224); out (n_groups, n_draws) C-contiguous, dtype of ll */
+int pla_group_sum(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws,
+                  int64_t stride_obs, int64_t stride_draw, const int64_t *group_offsets,
+                  const int64_t *group_members, int64_t n_groups, int mem_space, void *stream,
+                  void *out, int64_t *n_replaced /* may be NULL */);
+
+/* the LOGO pass (loo_group.py:216-300): group sums -> PSIS/SIS/TIS pass over the G rows; outputs per group,
+   agg as pla_psis_loo's over the groups */
+int pla_psis_loo_groups(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws,
+                        int64_t stride_obs, int64_t stride_draw, const int64_t *group_offsets,
+                        const int64_t *group_members, int64_t n_groups, int method, int64_t tail_count,
+                        double scale_value, double good_k, int mem_space, void *stream, double *diag,
+                        double *logo_i, double *lppd_i, double *agg, int64_t *n_replaced);
 
 /*
  * pla_e_loo -- PSIS-weighted expectations of a same-shape matrix and their function-specific Pareto k.

@@ -73,6 +73,10 @@ struct pla_engine {
   size_t d_probs_bytes = 0;
   void* d_rows = nullptr;  // clamped copy of a caller's device row-index list
   void* d_slab = nullptr;  // host path, observations-fastest input: (n_draws, block of observations) slab before the transpose
+  void* d_grp = nullptr;   // group sums of one block of groups (pla_psis_loo_groups; pla_group_sum from the host)
+  size_t d_grp_bytes = 0;
+  void* d_gidx = nullptr;  // host path of the group calls: [0] replaced-entry counter, then the uploaded offsets and members
+  size_t d_gidx_bytes = 0;
   size_t d_slab_bytes = 0;
   size_t d_rows_bytes = 0;
   // timing of the main kernel
@@ -330,6 +334,8 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_col) (void)hipFree(e->d_col);
   if (e->d_probs) (void)hipFree(e->d_probs);
   if (e->d_slab) (void)hipFree(e->d_slab);
+  if (e->d_grp) (void)hipFree(e->d_grp);
+  if (e->d_gidx) (void)hipFree(e->d_gidx);
   for (int i = 0; i < pla_engine::kTimingRing; ++i) {
     if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]);
     if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]);
@@ -553,6 +559,11 @@ static int stage_rows(pla_engine* eng, const void* ll, const int64_t* row_index,
   return PLA_OK;
 }
 
+static int psis_loo_run(pla_engine* eng, const void* ll, int dtype, int64_t n_src, const int64_t* row_index, int64_t n_obs,
+                        int64_t n_draws, int64_t stride_obs, int64_t stride_draw, int method, int64_t tail_count,
+                        double scale_value, double good_k, int mem_space, void* stream, double* diag, double* loo_i,
+                        double* lppd_i, double* agg);
+
 static int psis_loo_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, const int64_t* row_index, int64_t n_obs,
                          int64_t n_draws, int64_t stride_obs, int64_t stride_draw, int method, int64_t tail_count,
                          double scale_value, double good_k, int mem_space, void* stream, double* diag, double* loo_i,
@@ -565,6 +576,16 @@ static int psis_loo_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_s
     if (rc) return rc;
   }
   EngineCall call(eng, (hipStream_t)stream);
+  return psis_loo_run(eng, ll, dtype, n_src, row_index, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, scale_value,
+                      good_k, mem_space, stream, diag, loo_i, lppd_i, agg);
+}
+
+// the pass itself, for a caller that has checked the arguments and holds the engine (EngineCall)
+static int psis_loo_run(pla_engine* eng, const void* ll, int dtype, int64_t n_src, const int64_t* row_index, int64_t n_obs,
+                        int64_t n_draws, int64_t stride_obs, int64_t stride_draw, int method, int64_t tail_count,
+                        double scale_value, double good_k, int mem_space, void* stream, double* diag, double* loo_i,
+                        double* lppd_i, double* agg) {
+  int rc = PLA_OK;
   PLA_HIP(hipSetDevice(eng->device));
   hipStream_t s = (hipStream_t)stream;
   const size_t esz = dtype == PLA_F64 ? 8 : 4;
@@ -892,6 +913,212 @@ int pla_psis_loo_rows(pla_engine* eng, const void* ll, int dtype, int64_t n_obs,
   if (n_rows > 0 && !row_index) return fail(PLA_ERR_ARG, "row_index is NULL");
   return psis_loo_impl(eng, ll, dtype, n_obs, row_index, n_rows, n_draws, stride_obs, stride_draw, method, tail_count,
                        scale_value, good_k, mem_space, stream, diag, loo_i, lppd_i, agg);
+}
+
+// ---- leave-one-group-out (loo_group.py:216-300) ------------------------------------------------------------------------------
+// Group index: group_offsets[n_groups + 1], group_members[group_offsets[n_groups]], in the memory space of the matrix.  Host lists
+// are checked here; device lists are clamped by the group-sum kernel (pla_group.h).
+static int check_groups(const int64_t* offsets, const int64_t* members, int64_t n_groups, int64_t n_obs, int mem_space) {
+  if (n_groups < 0) return fail(PLA_ERR_ARG, "n_groups < 0");
+  if (!offsets) return fail(PLA_ERR_ARG, "group_offsets is NULL");
+  if (n_groups > 0 && n_obs < 1) return fail(PLA_ERR_ARG, "groups of an empty matrix");
+  if (mem_space == PLA_DEVICE) {
+    if (n_groups > 0 && !members) return fail(PLA_ERR_ARG, "group_members is NULL");
+    return PLA_OK;
+  }
+  if (offsets[0] != 0) return fail(PLA_ERR_ARG, "group_offsets[0] must be 0, got %lld", (long long)offsets[0]);
+  for (int64_t g = 0; g < n_groups; ++g)
+    if (offsets[g + 1] < offsets[g]) return fail(PLA_ERR_ARG, "group_offsets decrease at group %lld", (long long)g);
+  if (offsets[n_groups] > 0 && !members) return fail(PLA_ERR_ARG, "group_members is NULL");
+  for (int64_t g = 0; g < n_groups; ++g)
+    for (int64_t m = offsets[g]; m < offsets[g + 1]; ++m) {
+      if (members[m] < 0 || members[m] >= n_obs)
+        return fail(PLA_ERR_ARG, "group_members[%lld] = %lld is outside [0, %lld)", (long long)m, (long long)members[m], (long long)n_obs);
+      if (m > offsets[g] && members[m] < members[m - 1])
+        return fail(PLA_ERR_ARG, "the members of group %lld are not in ascending order", (long long)g);
+    }
+  return PLA_OK;
+}
+
+// groups per block of the group-sum buffer: sized like the ingest staging (4 GiB on the device -- PLA_INGEST_BLOCK_MB, a path
+// selector: the results do not depend on it -- and 1 GiB from the host)
+static int64_t group_block(int mem_space, int64_t n_groups, int64_t n_draws, size_t esz) {
+  const int64_t r = staged_chunk_rows(mem_space, true, n_groups, n_draws, esz);
+  return r > 0 ? r : 1;
+}
+
+// Device index lists are used as they are; host lists go up to the engine buffer behind the replaced-entry counter (word 0).
+static int group_index_on_device(pla_engine* eng, const int64_t* offsets, const int64_t* members, int64_t n_groups, int mem_space,
+                                 hipStream_t s, const int64_t** d_off, const int64_t** d_mem, unsigned long long** d_count) {
+  if (mem_space == PLA_DEVICE) {
+    *d_off = offsets;
+    *d_mem = members;
+    *d_count = nullptr;
+    return PLA_OK;
+  }
+  const int64_t nm = offsets[n_groups];
+  int rc = grow(&eng->d_gidx, &eng->d_gidx_bytes, (size_t)(1 + n_groups + 1 + nm) * sizeof(int64_t));
+  if (rc) return rc;
+  int64_t* d = (int64_t*)eng->d_gidx;
+  PLA_HIP(hipMemsetAsync(d, 0, sizeof(int64_t), s));
+  PLA_HIP(hipMemcpyAsync(d + 1, offsets, (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (nm > 0) PLA_HIP(hipMemcpyAsync(d + 2 + n_groups, members, (size_t)nm * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  *d_off = d + 1;
+  *d_mem = d + 2 + n_groups;
+  *d_count = (unsigned long long*)d;
+  return PLA_OK;
+}
+
+// Sums of groups [g0, g0 + ng) into `out` (device, (ng, n_draws) C-contiguous, dtype of ll).  Draws-contiguous device matrices are
+// read in place; observations-fastest device matrices are transposed block by block into the ingest staging, host matrices are
+// uploaded block by block (one pass over the matrix per call: a host matrix whose group sums exceed one block of groups is
+// read once per block).  The blocks go in ascending order and the kernel continues the partial sums, so the order of the adds
+// is NumPy's whatever the block sizes.
+static int group_sums_run(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                          int64_t stride_draw, const int64_t* d_off, const int64_t* d_mem, int64_t n_groups, int64_t g0, int64_t ng,
+                          int mem_space, hipStream_t s, void* out, unsigned long long* replaced) {
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  if (mem_space == PLA_DEVICE && stride_draw == 1) {
+    PLA_HIP(pla::launch_group_sum(ll, dtype, stride_obs, 0, n_obs, n_obs, false, true, (int)n_draws, d_off, d_mem, n_groups, g0, ng,
+                                  out, replaced, s));
+    eng->last_kernels = "group_sum_kernel (matrix read in place)";
+    return PLA_OK;
+  }
+  const bool obs_fastest = n_obs > 1 && n_draws > 1 && stride_obs == 1 && stride_draw >= n_obs;
+  if (!obs_fastest && !(mem_space == PLA_HOST && stride_draw == 1))
+    return fail(PLA_ERR_UNSUPPORTED, "group sums need unit stride along the draws, or along the observations");
+  const size_t row_bytes = (size_t)n_draws * esz;
+  const int64_t rows_per_chunk = mem_space == PLA_DEVICE ? staged_chunk_rows(mem_space, true, n_obs, n_draws, esz)
+                                                         : staged_chunk_rows(mem_space, false, n_obs, n_draws, esz);
+  int rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)rows_per_chunk * row_bytes);
+  if (rc) return rc;
+  const bool blocked = rows_per_chunk < n_obs;
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows_per_chunk) {
+    const int64_t nr = (n_obs - r0 < rows_per_chunk) ? (n_obs - r0) : rows_per_chunk;
+    if (mem_space == PLA_DEVICE) {
+      PLA_HIP(pla::launch_transpose_rows(ll, dtype, stride_draw, r0, nr, (int)n_draws, eng->d_in, s));
+    } else {
+      rc = stage_rows(eng, ll, nullptr, r0, nr, stride_obs, esz, row_bytes, s, stride_draw, dtype, rows_per_chunk);
+      if (rc) return rc;
+    }
+    PLA_HIP(pla::launch_group_sum(eng->d_in, dtype, n_draws, r0, nr, n_obs, blocked, r0 == 0, (int)n_draws, d_off, d_mem, n_groups, g0,
+                                  ng, out, replaced, s));
+    if (mem_space == PLA_HOST) PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next block
+  }
+  eng->last_kernels = mem_space == PLA_DEVICE ? "transpose_rows_kernel + group_sum_kernel (blocks of observations)"
+                                              : "group_sum_kernel (blocks of observations uploaded)";
+  return PLA_OK;
+}
+
+int pla_group_sum(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                  const int64_t* group_offsets, const int64_t* group_members, int64_t n_groups, int mem_space, void* stream, void* out,
+                  int64_t* n_replaced) {
+  int rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, PLA_SIS, 0, mem_space);
+  if (rc) return rc;
+  rc = check_groups(group_offsets, group_members, n_groups, n_obs, mem_space);
+  if (rc) return rc;
+  if (n_groups > 0 && !out) return fail(PLA_ERR_ARG, "out is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int64_t* d_off = nullptr;
+  const int64_t* d_mem = nullptr;
+  unsigned long long* d_count = nullptr;
+  rc = group_index_on_device(eng, group_offsets, group_members, n_groups, mem_space, s, &d_off, &d_mem, &d_count);
+  if (rc) return rc;
+  if (mem_space == PLA_DEVICE) {
+    if (n_replaced) PLA_HIP(hipMemsetAsync(n_replaced, 0, sizeof(int64_t), s));
+    TimedLaunch t(eng, s);  // (the group-sum kernel's own time: pla_engine_kernel_ms)
+    return group_sums_run(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, d_off, d_mem, n_groups, 0, n_groups, mem_space, s, out,
+                          (unsigned long long*)n_replaced);
+  }
+  const int64_t gb = group_block(mem_space, n_groups, n_draws, esz);
+  if (n_groups > 0) {
+    rc = grow(&eng->d_grp, &eng->d_grp_bytes, (size_t)gb * (size_t)n_draws * esz);
+    if (rc) return rc;
+  }
+  for (int64_t g0 = 0; g0 < n_groups; g0 += gb) {
+    const int64_t ng = n_groups - g0 < gb ? n_groups - g0 : gb;
+    rc = group_sums_run(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, d_off, d_mem, n_groups, g0, ng, mem_space, s, eng->d_grp,
+                        d_count);
+    if (rc) return rc;
+    PLA_HIP(hipMemcpyAsync((char*)out + (size_t)g0 * (size_t)n_draws * esz, eng->d_grp, (size_t)ng * (size_t)n_draws * esz,
+                           hipMemcpyDeviceToHost, s));
+  }
+  unsigned long long h = 0;
+  if (n_replaced) PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
+}
+
+int pla_psis_loo_groups(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                        int64_t stride_draw, const int64_t* group_offsets, const int64_t* group_members, int64_t n_groups, int method,
+                        int64_t tail_count, double scale_value, double good_k, int mem_space, void* stream, double* diag,
+                        double* logo_i, double* lppd_i, double* agg, int64_t* n_replaced) {
+  int rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, mem_space);
+  if (rc) return rc;
+  if (n_groups < 1) return fail(PLA_ERR_ARG, "n_groups < 1");
+  rc = check_groups(group_offsets, group_members, n_groups, n_obs, mem_space);
+  if (rc) return rc;
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int64_t* d_off = nullptr;
+  const int64_t* d_mem = nullptr;
+  unsigned long long* d_count = nullptr;
+  rc = group_index_on_device(eng, group_offsets, group_members, n_groups, mem_space, s, &d_off, &d_mem, &d_count);
+  if (rc) return rc;
+  if (mem_space == PLA_DEVICE) {
+    d_count = (unsigned long long*)n_replaced;
+    if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+  }
+  // pointwise outputs: the caller's device vectors, else (host calls, or agg without them) the engine scratch
+  double *dd = diag, *dl = logo_i, *dp = lppd_i;
+  if (mem_space == PLA_HOST || (agg && (!dd || !dl || !dp))) {
+    size_t have_b = eng->d_pw_elems * sizeof(double);
+    rc = grow((void**)&eng->d_pw, &have_b, (size_t)(3 * n_groups + PLA_AGG_COUNT) * sizeof(double));
+    eng->d_pw_elems = have_b / sizeof(double);
+    if (rc) return rc;
+    if (mem_space == PLA_HOST || !dd) dd = eng->d_pw;
+    if (mem_space == PLA_HOST || !dl) dl = eng->d_pw + n_groups;
+    if (mem_space == PLA_HOST || !dp) dp = eng->d_pw + 2 * n_groups;
+  }
+  // one block of groups at a time: its sums in the bounded buffer, the PSIS / SIS / TIS pass over them into its slices
+  const int64_t gb = group_block(mem_space, n_groups, n_draws, esz);
+  rc = grow(&eng->d_grp, &eng->d_grp_bytes, (size_t)gb * (size_t)n_draws * esz);
+  if (rc) return rc;
+  std::string label;
+  for (int64_t g0 = 0; g0 < n_groups; g0 += gb) {
+    const int64_t ng = n_groups - g0 < gb ? n_groups - g0 : gb;
+    rc = group_sums_run(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, d_off, d_mem, n_groups, g0, ng, mem_space, s,
+                        eng->d_grp, d_count);
+    if (rc) return rc;
+    const std::string sum_kernels = eng->last_kernels;
+    rc = psis_loo_run(eng, eng->d_grp, dtype, ng, nullptr, ng, n_draws, n_draws, 1, method, tail_count, scale_value, good_k, PLA_DEVICE,
+                      stream, dd ? dd + g0 : nullptr, dl ? dl + g0 : nullptr, dp ? dp + g0 : nullptr, nullptr);
+    if (rc) return rc;
+    if (g0 == 0) label = sum_kernels + " per block of groups, then " + eng->last_kernels;
+  }
+  eng->last_kernels = label;
+  // the aggregates once, over all groups
+  double* dagg = mem_space == PLA_HOST ? eng->d_pw + 3 * n_groups : agg;
+  if (agg) {
+    pla::ReduceParams rp{dd, dl, dp, n_groups, good_k, dagg, eng->counters + 1};
+    PLA_HIP(pla::launch_reduce(rp, eng->d_red, s));
+  }
+  if (mem_space == PLA_DEVICE) return PLA_OK;
+  if (diag) PLA_HIP(hipMemcpyAsync(diag, dd, n_groups * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (logo_i) PLA_HIP(hipMemcpyAsync(logo_i, dl, n_groups * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (lppd_i) PLA_HIP(hipMemcpyAsync(lppd_i, dp, n_groups * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (agg) PLA_HIP(hipMemcpyAsync(agg, dagg, PLA_AGG_COUNT * sizeof(double), hipMemcpyDeviceToHost, s));
+  unsigned long long h = 0;
+  if (n_replaced) PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
 }
 
 int pla_importance_weights(pla_engine* eng, const void* logw, int dtype, int64_t n_obs, int64_t n_draws,

@@ -119,6 +119,12 @@ hipError_t launch_tile(const RowsParams& p, int dtype, int ks, hipStream_t strea
 // WAIC on an observations-fastest matrix read in place, one lane per observation (element (i, s) at in[s * ld + i])
 hipError_t launch_waic_col(const void* in, int dtype, int64_t n_obs, int n_draws, int64_t ld, double scale_value, double* lppd_i,
                            double* var_i, double* waic_i, unsigned long long* replaced, hipStream_t stream);
+// group sums of the leave-one-group-out pass (pla_group.h): out[g - g0, s] = sum of ll[m, s] over the members of group g in
+// ascending order (NumPy's order), groups [g0, g0 + n_groups); the rows come from `in` = observations [row0, row0 + n_rows) of the
+// matrix, draws contiguous (blocked: one of several blocks, partial sums continued in `out`).  replaced: NaN entries (may be null)
+hipError_t launch_group_sum(const void* in, int dtype, int64_t stride_obs, int64_t row0, int64_t n_rows, int64_t n_src, bool blocked,
+                            bool first_block, int n_draws, const int64_t* offsets, const int64_t* members, int64_t n_groups_total,
+                            int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream);
 // largest tail count the kernels accept
 int max_tail_count();
 

@@ -1,9 +1,9 @@
 """``ELPDData``: the result object of ``loo()`` -- a ``pandas.Series`` with a report printer.
 
 Mirrors the LOO part of the reference container (pyloo/elpd.py:100-498): same index keys,
-same properties, same printed report (README.md:76-84 of the reference), including the Pareto-k
+same properties, same printed report (README.md:76-84 of the reference; the LOGO report of elpd.py:165-220), including the Pareto-k
 table with bins ``(-inf, good_k], (good_k, 1], (1, inf)`` (elpd.py:300-330).  The k-fold,
-LOGO, sub-sampling and non-factorised report variants are out of scope.
+sub-sampling and non-factorised report variants are out of scope.
 """
 
 from copy import copy as _copy
@@ -26,6 +26,14 @@ Computed from {n_samples} posterior samples and {n_points} observations log-like
           Estimate       SE
 elpd_waic   {elpd:<8.2f}    {se:<.2f}
 p_waic       {p_waic:<8.2f}        -"""
+
+_LOGO_REPORT = """
+Computed from {n_samples} posterior samples and {n_groups} groups log-likelihood matrix.
+
+         Estimate       SE
+elpd_logo   {elpd:<8.2f}    {se:<.2f}
+p_logo       {p_logo:<8.2f}    {p_logo_se:<.2f}
+logoic      {logoic:<8.2f}    {logoic_se:<.2f}"""
 
 _K_TABLE = """
 ------
@@ -62,6 +70,8 @@ class ELPDData(pd.Series):
             text = _WAIC_REPORT.format(n_samples=self.n_samples, n_points=self.n_data_points, elpd=self["elpd_waic"],
                                        se=self["se"], p_waic=self["p_waic"])
             return text + (_WARNED if self.warning else "")
+        if kind == "logo":
+            return self._logo_report()
         if kind != "loo":
             raise ValueError("Invalid ELPDData object")
         tail = ""
@@ -84,6 +94,24 @@ class ELPDData(pd.Series):
         if self.warning:
             text += _WARNED
         return text + tail
+
+    def _logo_report(self):
+        """elpd.py:165-220: LOGO_BASE_FMT, the warning line, then the Pareto-k table (or the all-good line) when k is there."""
+        text = _LOGO_REPORT.format(n_samples=self.n_samples, n_groups=self["n_groups"], elpd=self["elpd_logo"], se=self["se"],
+                                   p_logo=self["p_logo"], p_logo_se=self.get("p_logo_se", float("nan")), logoic=self["logoic"],
+                                   logoic_se=self["logoic_se"])
+        if self.warning:
+            text += _WARNED
+        if "pareto_k" in self and self.get("good_k", None) is not None:
+            gk = self["good_k"]
+            kv = np.asarray(getattr(self["pareto_k"], "values", self["pareto_k"]), dtype=float).ravel()
+            counts = np.histogram(kv, bins=np.asarray([-np.inf, gk, 1, np.inf]))[0]
+            if counts[1] == 0 and counts[2] == 0:
+                text += _ALL_GOOD.format(gk=gk)
+            else:
+                pct = counts / counts.sum() * 100
+                text += _K_TABLE.format(gk=gk, c0=int(counts[0]), c1=int(counts[1]), c2=int(counts[2]), p0=pct[0], p1=pct[1], p2=pct[2])
+        return text
 
     def __repr__(self):
         return self.__str__()

@@ -186,6 +186,96 @@ class Engine:
                                      self._stream(), p(diag), p(loo_i), p(lppd_i), p(agg)))
         return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg}
 
+    # ------------------------------------------------------------------ leave-one-group-out
+    @staticmethod
+    def _host_index(index):
+        """(offsets, members) of a GroupIndex as contiguous host int64 arrays."""
+        conv = lambda a: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a), dtype=np.int64)  # noqa: E731
+        return conv(index.offsets), conv(index.members)
+
+    @staticmethod
+    def _device_index(index, device):
+        import torch
+
+        conv = lambda a: (a if _is_torch_tensor(a) else torch.from_numpy(np.asarray(a))).to(device=device, dtype=torch.int64).contiguous()  # noqa: E731
+        return conv(index.offsets), conv(index.members)
+
+    def _groups_input(self, ll):
+        import torch
+
+        if ll.dim() != 2 or not ll.is_cuda:
+            raise ValueError("expected a 2-D CUDA tensor")
+        if ll.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"unsupported dtype {ll.dtype}")
+        return self._library_layout(ll)
+
+    def group_sum(self, ll, index):
+        """(n_obs, n_draws) matrix + :class:`~pyloo_amd.loo_group.GroupIndex` -> ``(sums, n_replaced)`` (``pla_group_sum``):
+        ``sums[g]`` = the rows of group g's members added in ascending order, in the matrix's dtype (bitwise NumPy's
+        ``ll[members].sum(axis=0)``), NaN counted as -1e10.  NumPy in -> ``(ndarray, int)``; CUDA tensor in -> ``(tensor, int64
+        tensor of one element)``, nothing synchronised."""
+        G = int(index.n_groups)
+        if _is_torch_tensor(ll):
+            import torch
+
+            t = self._groups_input(ll)
+            n, s = t.shape
+            off, mem = self._device_index(index, t.device)
+            out = torch.empty((G, s), dtype=t.dtype, device=t.device)
+            nrep = torch.zeros(1, dtype=torch.int64, device=t.device)
+            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            check(self._lib.pla_group_sum(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
+                                          C.c_void_p(off.data_ptr()), C.c_void_p(mem.data_ptr()), G, PLA_DEVICE, self._stream(),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(nrep.data_ptr())))
+            return out, nrep
+        a = self._as_2d_host(ll, allow_obs_fastest=True)
+        n, s = a.shape
+        so, sd = self._host_strides(a)
+        off, mem = self._host_index(index)
+        out = np.empty((G, s), dtype=a.dtype)
+        nrep = C.c_int64(0)
+        check(self._lib.pla_group_sum(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd,
+                                      off.ctypes.data_as(C.c_void_p), mem.ctypes.data_as(C.c_void_p), G, PLA_HOST, None,
+                                      out.ctypes.data_as(C.c_void_p), C.byref(nrep)))
+        return out, int(nrep.value)
+
+    def psis_loo_groups(self, ll, index, tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True):
+        """Leave-one-group-out pass (``pla_psis_loo_groups``): group sums, then the PSIS / SIS / TIS pass over them.
+
+        Returns ``dict(diag, logo_i, lppd_i, agg, n_replaced)`` with one pointwise entry per group -- NumPy arrays (and an int)
+        for NumPy input, CUDA tensors for CUDA-tensor input (nothing synchronised)."""
+        mcode = METHOD_CODES[method]
+        G = int(index.n_groups)
+        if _is_torch_tensor(ll):
+            import torch
+
+            t = self._groups_input(ll)
+            n, s = t.shape
+            dev = t.device
+            off, mem = self._device_index(index, dev)
+            mk = lambda: torch.empty(G, dtype=torch.float64, device=dev)  # noqa: E731
+            diag, logo_i, lppd_i = (mk(), mk(), mk()) if (pointwise or aggregate) else (None, None, None)
+            agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev) if aggregate else None
+            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
+            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            check(self._lib.pla_psis_loo_groups(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1), p(off), p(mem),
+                                                G, mcode, int(tail_count), float(scale_value), float(good_k), PLA_DEVICE,
+                                                self._stream(), p(diag), p(logo_i), p(lppd_i), p(agg), p(nrep)))
+            return {"diag": diag, "logo_i": logo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": nrep}
+        a = self._as_2d_host(ll, allow_obs_fastest=True)
+        n, s = a.shape
+        so, sd = self._host_strides(a)
+        off, mem = self._host_index(index)
+        diag, logo_i, lppd_i = (np.empty(G), np.empty(G), np.empty(G)) if pointwise else (None, None, None)
+        agg = np.zeros(AGG_COUNT) if aggregate else None
+        nrep = C.c_int64(0)
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        check(self._lib.pla_psis_loo_groups(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd, p(off), p(mem), G,
+                                            mcode, int(tail_count), float(scale_value), float(good_k), PLA_HOST, None, p(diag),
+                                            p(logo_i), p(lppd_i), p(agg), C.byref(nrep)))
+        return {"diag": diag, "logo_i": logo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": int(nrep.value)}
+
     # ------------------------------------------------------------------ weights pass
     def importance_weights(self, logw, tail_count=0, method="psis"):
         """(n_obs, n_draws) log ratios -> (lw, diag) (``pla_importance_weights``)."""
