@@ -265,7 +265,7 @@ int pla_engine_kernel_ms(pla_engine *eng, double *total_ms, int64_t *launches);
  * wave kernel up to the tail selection); device-pointer calls only.  Read it before or after pla_engine_kernel_ms. */
 int pla_engine_first_kernel_ms(pla_engine *eng, double *total_ms, int64_t *launches);
 
-/* Which kernels the engine's last PSIS-LOO / weights call launched, as text ("wave_loo_kernel<double> (streamed) +
+/* Which kernels the engine's last PSIS-LOO / weights / group / e_loo call launched, as text ("wave_loo_kernel<double> (streamed) +
  * fit_rows_stream_kernel beside it + ..."): for benchmark records, so that what a roofline line names is what ran.
  * Copies at most cap - 1 characters and a terminating 0 into buf. */
 int pla_engine_last_kernels(pla_engine *eng, char *buf, int cap);

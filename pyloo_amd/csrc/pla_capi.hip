@@ -1405,6 +1405,7 @@ int pla_e_loo(pla_engine* eng, const void* x, const void* log_weights, const voi
   if (mem_space == PLA_DEVICE) {
     PLA_HIP(pla::launch_e_loo(x, log_weights, log_ratios, dtype, n_obs, (int)n_draws, stride_obs, stride_draw, (int)tail_len, mean,
                               variance, k_mean, k_var, k_ratio, (unsigned*)eng->d_slow, eng->counters, s));
+    eng->last_kernels = pla::last_rows_kernels();
     return PLA_OK;
   }
   // ---- PLA_HOST: row blocks of the two or three matrices through the staging buffers (d_in: x, d_lw: log-weights, d_slab: ratios)
@@ -1435,6 +1436,7 @@ int pla_e_loo(pla_engine* eng, const void* x, const void* log_weights, const voi
     double* d = eng->d_pw;
     PLA_HIP(pla::launch_e_loo(eng->d_in, eng->d_lw, log_ratios ? eng->d_slab : nullptr, dtype, nr, (int)n_draws, n_draws, 1, (int)tail_len,
                               d, d + nr, d + 2 * nr, d + 3 * nr, d + 4 * nr, (unsigned*)eng->d_slow, eng->counters, s));
+    eng->last_kernels = pla::last_rows_kernels();
     for (int k = 0; k < 5; ++k)
       if (out[k]) PLA_HIP(hipMemcpyAsync(out[k] + r0, d + k * nr, (size_t)nr * sizeof(double), hipMemcpyDeviceToHost, s));
     PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
@@ -1469,6 +1471,7 @@ int pla_e_loo_quantiles(pla_engine* eng, const void* x, const void* log_weights,
     if (rc) return rc;
     PLA_HIP(pla::launch_e_loo_quantiles(x, log_weights, dtype, n_obs, (int)n_draws, stride_obs, stride_draw, dp, (int)n_probs, out,
                                         (unsigned*)eng->d_slow, eng->counters, s));
+    eng->last_kernels = pla::last_rows_kernels();
     return PLA_OK;
   }
   if (stride_draw != 1) return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST input needs stride_draw == 1");
@@ -1495,6 +1498,7 @@ int pla_e_loo_quantiles(pla_engine* eng, const void* x, const void* log_weights,
     PLA_HIP(hipMemcpy2DAsync(eng->d_lw, row_bytes, (const char*)log_weights + off, pitch, row_bytes, (size_t)nr, hipMemcpyHostToDevice, s));
     PLA_HIP(pla::launch_e_loo_quantiles(eng->d_in, eng->d_lw, dtype, nr, (int)n_draws, n_draws, 1, dp, (int)n_probs, eng->d_pw,
                                         (unsigned*)eng->d_slow, eng->counters, s));
+    eng->last_kernels = pla::last_rows_kernels();
     PLA_HIP(hipMemcpyAsync(out + r0 * n_probs, eng->d_pw, (size_t)(nr * n_probs) * sizeof(double), hipMemcpyDeviceToHost, s));
     PLA_HIP(hipStreamSynchronize(s));
   }

@@ -103,6 +103,9 @@ __device__ __forceinline__ void e_loo_finish(const ELooParams& P, const int64_t 
     if (xdev <= kCloseAtol + kCloseRtol * fabs(x0) && !(flags & 4u)) v = 0.0;      // e_loo.py:520-521
     else if (fabs(wss - 1.0) <= kCloseAtol + kCloseRtol * 1.0) v = 0.0;             // 523-525
     else {
+      // mean ** 2 is rounded on its own, as numpy does: contracted into an fma, an inf msq minus a mean whose square
+      // overflows came out inf instead of the reference's NaN
+#pragma clang fp contract(off)
       v = (msq - mean * mean) / (1.0 - wss);                                          // 527-530
       v = (0.0 > v) ? 0.0 : v;  // Python's max(var, 0.0): a NaN variance stays NaN    531
     }

@@ -27,6 +27,8 @@ hipError_t launch_e_loo(const void* x, const void* lw, const void* lr, int dtype
     int64_t wg = (n_obs + 3) / 4;
     if (wg > 8192) wg = 8192;
     const bool own = lr && lr != lw;
+    note_kernels("e_loo_wave_kernel<%s, %s> + e_loo_rows_kernel<%s, 256, list> (declined rows)", dtype_name(dtype),
+                 own ? "own ratios" : "ratios = log-weights", dtype_name(dtype));
     if (dtype == PLA_F64) {
       if (own) hipLaunchKernelGGL((e_loo_wave_kernel<double, true>), dim3((unsigned)wg), dim3(256), 0, stream, p);
       else hipLaunchKernelGGL((e_loo_wave_kernel<double, false>), dim3((unsigned)wg), dim3(256), 0, stream, p);
@@ -41,6 +43,7 @@ hipError_t launch_e_loo(const void* x, const void* lw, const void* lr, int dtype
     else hipLaunchKernelGGL((e_loo_rows_kernel<float, 256, true>), dim3((unsigned)g2), dim3(256), 0, stream, p);
     return hipGetLastError();
   }
+  note_kernels("e_loo_rows_kernel<%s, 256> (one workgroup per observation)", dtype_name(dtype));
   if (dtype == PLA_F64) hipLaunchKernelGGL((e_loo_rows_kernel<double, 256>), dim3((unsigned)grid), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL((e_loo_rows_kernel<float, 256>), dim3((unsigned)grid), dim3(256), 0, stream, p);
   return hipGetLastError();
@@ -69,6 +72,10 @@ hipError_t launch_e_loo_quantiles(const void* x, const void* lw, int dtype, int6
     if (e != hipSuccess) return e;
   }
   const int64_t g2 = wave ? (n_obs < 2048 ? n_obs : 2048) : (n_obs < 16384 ? n_obs : 16384);
+  if (wave)
+    note_kernels("e_loo_quantile_wave_kernel<%s> + e_loo_quantile_kernel<%s, 512> (declined rows)", dtype_name(dtype), dtype_name(dtype));
+  else
+    note_kernels("e_loo_quantile_kernel<%s, 512> (one workgroup per observation)", dtype_name(dtype));
   if (dtype == PLA_F64) hipLaunchKernelGGL((e_loo_quantile_kernel<double, 512>), dim3((unsigned)g2), dim3(512), 0, stream, p);
   else hipLaunchKernelGGL((e_loo_quantile_kernel<float, 512>), dim3((unsigned)g2), dim3(512), 0, stream, p);
   return hipGetLastError();

@@ -475,7 +475,7 @@ class Engine:
         return ms.value, k.value
 
     def last_kernels(self):
-        """Which kernels the last PSIS-LOO / weights call launched (text; for benchmark records)."""
+        """Which kernels the last PSIS-LOO / weights / group / e_loo call launched (text; for benchmark records and tests)."""
         buf = C.create_string_buffer(512)
         check(self._lib.pla_engine_last_kernels(self._h, buf, 512))
         return buf.value.decode("utf-8", "replace")
