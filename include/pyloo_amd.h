@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PLA_ABI_VERSION 5
+#define PLA_ABI_VERSION 6
 
 /* status codes */
 #define PLA_OK 0
@@ -255,6 +255,44 @@ int pla_e_loo(pla_engine *eng, const void *x, const void *log_weights, const voi
 int pla_e_loo_quantiles(pla_engine *eng, const void *x, const void *log_weights, int dtype, int64_t n_obs,
                         int64_t n_draws, int64_t stride_obs, int64_t stride_draw, const double *probs,
                         int64_t n_probs, int mem_space, void *stream, double *out);
+
+/*
+ * Model comparison -- loo_compare's weights and standard errors (compare.py:205-229, 477-577).
+ * The pointwise values of K models (loo_i / waic_i) as a (n_models, n_obs) matrix `x`: row k at x + k * pitch (ELEMENTS), dtype
+ * PLA_F64 or PLA_F32 (promoted on load), in `mem_space` (a host matrix is uploaded once per call).  1 <= n_models <=
+ * PLA_COMPARE_MAX_MODELS (more: PLA_ERR_UNSUPPORTED); 1 <= n_obs < 2^32.  `scale_mul` multiplies every value on load: 1 ("log"), -1
+ * ("negative_log") or -0.5 ("deviance") bring a table to the log scale as compare.py:489-492 / 556-559 do.  Every reduction goes
+ * through fixed per-tile partials in engine workspace, combined in tile order (csrc/pla_compare.h): two calls on the same input give
+ * the same bits, whatever the grid or the device.
+ *
+ * pla_compare_moments  the diff / dse arithmetic of compare.py:214-229.  out [3 * n_models + 1] double, memory space of x:
+ *                      out[3k] = sum_i x_ik, out[3k+1] = mean_i d_ik, out[3k+2] = sum_i (d_ik - mean)^2 with d_ik = x_ik - x_{best,i}
+ *                      (dse_k = sqrt(N * var(d_k)) = sqrt(out[3k+2]): compare.py:226-227), out[3K] = sum_i max_k x_ik.  The values are
+ *                      taken as they are (the dse is on the table's own scale).
+ * pla_stacking_eval    one evaluation of the stacking objective and its gradient (compare.py:494-514) at the weights w [n_models]
+ *                      (HOST array): with m_i = max_k x'_ik, e_ik = exp(x'_ik - m_i), d_i = sum_k w_k e_ik:  out[0] = sum_i log d_i,
+ *                      out[1 + k] = sum_i e_ik / d_i.  out [n_models + 1] is a HOST array; the call synchronises `stream`.
+ * pla_bb_bootstrap     the Bayesian bootstrap of compare.py:551-571 without its (n_boot, n_obs) Dirichlet matrix: z [n_boot][n_models],
+ *                      memory space of x, z_bk = n_obs * scale_mul * sum_i G_bi x_ik / sum_i G_bi with G_bi ~ Gamma(alpha, 1) drawn in
+ *                      the kernel from the Philox4x32-10 stream specified in csrc/pla_compare.h (key = seed, counter = (i, b, attempt,
+ *                      sub-block): a pure function of (seed, alpha, b, i)).  alpha > 0, 1 <= n_boot <= 2^32.  The partials of up to
+ *                      64 MiB of replicates live in engine workspace; more replicates run in several launches.
+ * pla_bb_gamma_draws   the same stream on its own, for tests: out [n_boot][n_obs] double (memory space mem_space) = G_bi,
+ *                      n_boot * n_obs <= 2^31.
+ * pla_engine_set_compare_grid  caps the workgroups per launch of the three passes above (0: the library's choice); the results do not
+ *                      depend on it.
+ */
+#define PLA_COMPARE_MAX_MODELS 64
+int pla_compare_moments(pla_engine *eng, const void *x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch,
+                        int64_t best, int mem_space, void *stream, double *out);
+int pla_stacking_eval(pla_engine *eng, const void *x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch,
+                      double scale_mul, const double *weights, int mem_space, void *stream, double *out);
+int pla_bb_bootstrap(pla_engine *eng, const void *x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch,
+                     double scale_mul, int64_t n_boot, double alpha, uint64_t seed, int mem_space, void *stream,
+                     double *z);
+int pla_bb_gamma_draws(pla_engine *eng, uint64_t seed, double alpha, int64_t n_boot, int64_t n_obs, int mem_space,
+                       void *stream, double *out);
+int pla_engine_set_compare_grid(pla_engine *eng, int max_workgroups);
 
 /* Timing of the dominant kernel, measured with hipEvents on the launch stream.
  * enable != 0 brackets every main-kernel launch with events; pla_engine_kernel_ms returns the

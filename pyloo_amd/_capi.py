@@ -12,7 +12,7 @@ PLA_PSIS, PLA_SIS, PLA_TIS = 0, 1, 2
 METHOD_CODES = {"psis": PLA_PSIS, "sis": PLA_SIS, "tis": PLA_TIS}
 AGG_N, AGG_SUM_LOO, AGG_M2_LOO, AGG_SUM_LPPD, AGG_N_HIGH, AGG_N_NONFINITE, AGG_MIN_DIAG, AGG_N_SLOW = range(8)
 AGG_COUNT = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # every symbol declared in include/pyloo_amd.h
 SYMBOLS = (
@@ -22,6 +22,7 @@ SYMBOLS = (
     "pla_engine_set_frozen", "pla_engine_set_timing", "pla_engine_kernel_ms", "pla_engine_first_kernel_ms", "pla_fill_synthetic",
     "pla_engine_last_kernels", "pla_aggregate_pack", "pla_aggregate_merge", "pla_fill_synthetic_chains",
     "pla_env_overrides", "pla_engine_stream_stats", "pla_group_sum", "pla_psis_loo_groups",
+    "pla_compare_moments", "pla_stacking_eval", "pla_bb_bootstrap", "pla_bb_gamma_draws", "pla_engine_set_compare_grid",
 )
 
 
@@ -86,6 +87,11 @@ def load_library():
     lib.pla_engine_stream_stats.argtypes = [vp, C.POINTER(i64)]
     lib.pla_group_sum.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, vp, i64, ci, vp, vp, vp]
     lib.pla_psis_loo_groups.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, vp, i64, ci, i64, dbl, dbl, ci, vp, vp, vp, vp, vp, vp]
+    lib.pla_compare_moments.argtypes = [vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
+    lib.pla_stacking_eval.argtypes = [vp, vp, ci, i64, i64, i64, dbl, vp, ci, vp, vp]
+    lib.pla_bb_bootstrap.argtypes = [vp, vp, ci, i64, i64, i64, dbl, i64, dbl, C.c_uint64, ci, vp, vp]
+    lib.pla_bb_gamma_draws.argtypes = [vp, C.c_uint64, dbl, i64, i64, ci, vp, vp]
+    lib.pla_engine_set_compare_grid.argtypes = [vp, ci]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

@@ -79,6 +79,11 @@ struct pla_engine {
   size_t d_gidx_bytes = 0;
   size_t d_slab_bytes = 0;
   size_t d_rows_bytes = 0;
+  void* d_cmp = nullptr;  // model comparison: per-tile partials (pla_compare.h)
+  size_t d_cmp_bytes = 0;
+  void* d_cmp_out = nullptr;  // ... and the outputs of host calls / of the stacking evaluation
+  size_t d_cmp_out_bytes = 0;
+  int compare_grid = 0;  // pla_engine_set_compare_grid: workgroup cap of the comparison passes (0: the library's choice)
   // timing of the main kernel
   bool timing = false;
   static constexpr int kTimingRing = 64;  // launches timed without a host-side wait in between
@@ -336,6 +341,8 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_slab) (void)hipFree(e->d_slab);
   if (e->d_grp) (void)hipFree(e->d_grp);
   if (e->d_gidx) (void)hipFree(e->d_gidx);
+  if (e->d_cmp) (void)hipFree(e->d_cmp);
+  if (e->d_cmp_out) (void)hipFree(e->d_cmp_out);
   for (int i = 0; i < pla_engine::kTimingRing; ++i) {
     if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]);
     if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]);
@@ -1118,6 +1125,185 @@ int pla_psis_loo_groups(pla_engine* eng, const void* ll, int dtype, int64_t n_ob
   if (n_replaced) PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
   PLA_HIP(hipStreamSynchronize(s));
   if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
+}
+
+// ---- model comparison (compare.py:205-229, 477-577) ----------------------------------------------------------------------------
+static int compare_check(pla_engine* eng, const void* x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch, int mem_space) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (!x) return fail(PLA_ERR_ARG, "input pointer is NULL");
+  if (n_obs < 1 || n_obs >= ((int64_t)1 << 32)) return fail(PLA_ERR_ARG, "n_obs must lie in [1, 2^32), got %lld", (long long)n_obs);
+  if (n_models < 1) return fail(PLA_ERR_ARG, "n_models < 1");
+  if (n_models > PLA_COMPARE_MAX_MODELS)
+    return fail(PLA_ERR_UNSUPPORTED, "n_models = %lld exceeds the device limit of %d models", (long long)n_models, PLA_COMPARE_MAX_MODELS);
+  if (n_models > 1 && pitch < n_obs) return fail(PLA_ERR_ARG, "pitch %lld < n_obs %lld", (long long)pitch, (long long)n_obs);
+  return PLA_OK;
+}
+
+// the (K, N) matrix on the device: device pointers as they are, host matrices uploaded once into the ingest staging (C-contiguous)
+static int compare_input_on_device(pla_engine* eng, const void* x, int dtype, int64_t K, int64_t N, int64_t pitch, int mem_space,
+                                   hipStream_t s, const void** dx, int64_t* dpitch) {
+  if (mem_space == PLA_DEVICE) {
+    *dx = x;
+    *dpitch = K > 1 ? pitch : N;
+    return PLA_OK;
+  }
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  int rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)K * (size_t)N * esz);
+  if (rc) return rc;
+  PLA_HIP(hipMemcpy2DAsync(eng->d_in, (size_t)N * esz, x, (size_t)(K > 1 ? pitch : N) * esz, (size_t)N * esz, (size_t)K,
+                           hipMemcpyHostToDevice, s));
+  *dx = eng->d_in;
+  *dpitch = N;
+  return PLA_OK;
+}
+
+static const char* compare_where(int mem_space) { return mem_space == PLA_DEVICE ? "(matrix read in place)" : "(matrix uploaded)"; }
+
+int pla_engine_set_compare_grid(pla_engine* eng, int max_workgroups) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (max_workgroups < 0) return fail(PLA_ERR_ARG, "max_workgroups < 0");
+  EngineCall call(eng);
+  eng->compare_grid = max_workgroups;
+  return PLA_OK;
+}
+
+int pla_compare_moments(pla_engine* eng, const void* x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch, int64_t best,
+                        int mem_space, void* stream, double* out) {
+  int rc = compare_check(eng, x, dtype, n_models, n_obs, pitch, mem_space);
+  if (rc) return rc;
+  if (best < 0 || best >= n_models) return fail(PLA_ERR_ARG, "best = %lld is not a model index", (long long)best);
+  if (!out) return fail(PLA_ERR_ARG, "out is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int K = (int)n_models;
+  const int64_t tiles = pla::compare_n_tiles(n_obs);
+  rc = grow(&eng->d_cmp, &eng->d_cmp_bytes, (size_t)tiles * (size_t)(3 * K + 2) * sizeof(double));
+  if (rc) return rc;
+  double* dout = out;
+  if (mem_space == PLA_HOST) {
+    rc = grow(&eng->d_cmp_out, &eng->d_cmp_out_bytes, (size_t)(3 * K + 1) * sizeof(double));
+    if (rc) return rc;
+    dout = (double*)eng->d_cmp_out;
+  }
+  const void* dx = nullptr;
+  int64_t dp = 0;
+  rc = compare_input_on_device(eng, x, dtype, K, n_obs, pitch, mem_space, s, &dx, &dp);
+  if (rc) return rc;
+  {
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_compare_moments(dx, dtype, dp, K, n_obs, (int)best, (double*)eng->d_cmp, dout, eng->compare_grid, s));
+  }
+  eng->last_kernels = std::string("compare_moments_kernel<") + pla::dtype_name(dtype) + "> + compare_moments_final_kernel " +
+                      compare_where(mem_space);
+  if (mem_space == PLA_DEVICE) return PLA_OK;
+  PLA_HIP(hipMemcpyAsync(out, dout, (size_t)(3 * K + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  return PLA_OK;
+}
+
+int pla_stacking_eval(pla_engine* eng, const void* x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch, double scale_mul,
+                      const double* weights, int mem_space, void* stream, double* out) {
+  int rc = compare_check(eng, x, dtype, n_models, n_obs, pitch, mem_space);
+  if (rc) return rc;
+  if (!weights || !out) return fail(PLA_ERR_ARG, "weights / out is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int K = (int)n_models;
+  const int64_t tiles = pla::compare_n_tiles(n_obs);
+  rc = grow(&eng->d_cmp, &eng->d_cmp_bytes, (size_t)tiles * (size_t)(K + 1) * sizeof(double));
+  if (rc) return rc;
+  rc = grow(&eng->d_cmp_out, &eng->d_cmp_out_bytes, (size_t)(2 * K + 1) * sizeof(double));  // out [K + 1], then the weights
+  if (rc) return rc;
+  const void* dx = nullptr;
+  int64_t dp = 0;
+  rc = compare_input_on_device(eng, x, dtype, K, n_obs, pitch, mem_space, s, &dx, &dp);
+  if (rc) return rc;
+  double* dw = (double*)eng->d_cmp_out + K + 1;
+  PLA_HIP(hipMemcpyAsync(dw, weights, (size_t)K * sizeof(double), hipMemcpyHostToDevice, s));
+  {
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_stacking_eval(dx, dtype, dp, K, n_obs, scale_mul, dw, (double*)eng->d_cmp, (double*)eng->d_cmp_out,
+                                      eng->compare_grid, s));
+  }
+  eng->last_kernels = std::string("stacking_eval_kernel<") + pla::dtype_name(dtype) + "> + compare_tiles_sum_kernel " +
+                      compare_where(mem_space);
+  PLA_HIP(hipMemcpyAsync(out, eng->d_cmp_out, (size_t)(K + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  return PLA_OK;
+}
+
+int pla_bb_bootstrap(pla_engine* eng, const void* x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch, double scale_mul,
+                     int64_t n_boot, double alpha, uint64_t seed, int mem_space, void* stream, double* z) {
+  int rc = compare_check(eng, x, dtype, n_models, n_obs, pitch, mem_space);
+  if (rc) return rc;
+  if (n_boot < 1 || n_boot > ((int64_t)1 << 32)) return fail(PLA_ERR_ARG, "n_boot must lie in [1, 2^32], got %lld", (long long)n_boot);
+  if (!(alpha > 0.0) || !std::isfinite(alpha)) return fail(PLA_ERR_ARG, "alpha must be a positive number");
+  if (!z) return fail(PLA_ERR_ARG, "z is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int K = (int)n_models;
+  const int64_t tiles = pla::compare_n_tiles(n_obs);
+  // replicates per launch: their partials within 64 MiB (whole blocks of 64)
+  const size_t per_rep = (size_t)tiles * (size_t)(K + 1) * sizeof(double);
+  int64_t nb = (int64_t)(((size_t)64 << 20) / per_rep) / 64 * 64;
+  if (nb < 64) nb = 64;
+  if (nb > n_boot) nb = n_boot;
+  rc = grow(&eng->d_cmp, &eng->d_cmp_bytes, (size_t)nb * per_rep);
+  if (rc) return rc;
+  if (mem_space == PLA_HOST) {
+    rc = grow(&eng->d_cmp_out, &eng->d_cmp_out_bytes, (size_t)nb * (size_t)K * sizeof(double));
+    if (rc) return rc;
+  }
+  const void* dx = nullptr;
+  int64_t dp = 0;
+  rc = compare_input_on_device(eng, x, dtype, K, n_obs, pitch, mem_space, s, &dx, &dp);
+  if (rc) return rc;
+  for (int64_t b0 = 0; b0 < n_boot; b0 += nb) {
+    const int64_t n = n_boot - b0 < nb ? n_boot - b0 : nb;
+    double* zb = mem_space == PLA_DEVICE ? z + b0 * K : (double*)eng->d_cmp_out;
+    {
+      TimedLaunch t(eng, s);
+      PLA_HIP(pla::launch_bb_bootstrap(dx, dtype, dp, K, n_obs, scale_mul, seed, alpha, b0, n, (double*)eng->d_cmp, zb, eng->compare_grid,
+                                       s));
+    }
+    if (mem_space == PLA_HOST) {
+      PLA_HIP(hipMemcpyAsync(z + b0 * K, zb, (size_t)n * (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
+      PLA_HIP(hipStreamSynchronize(s));  // the buffer is reused by the next block
+    }
+  }
+  eng->last_kernels = std::string("bb_bootstrap_kernel<") + pla::dtype_name(dtype) + "> + bb_final_kernel " + compare_where(mem_space);
+  return PLA_OK;
+}
+
+int pla_bb_gamma_draws(pla_engine* eng, uint64_t seed, double alpha, int64_t n_boot, int64_t n_obs, int mem_space, void* stream,
+                       double* out) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (n_boot < 1 || n_boot > ((int64_t)1 << 32) || n_obs < 1 || n_obs >= ((int64_t)1 << 32) || n_boot * n_obs > ((int64_t)1 << 31))
+    return fail(PLA_ERR_ARG, "need 1 <= n_boot <= 2^32, 1 <= n_obs < 2^32 and n_boot * n_obs <= 2^31");
+  if (!(alpha > 0.0) || !std::isfinite(alpha)) return fail(PLA_ERR_ARG, "alpha must be a positive number");
+  if (!out) return fail(PLA_ERR_ARG, "out is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)n_boot * (size_t)n_obs * sizeof(double);
+  double* d = out;
+  if (mem_space == PLA_HOST) {
+    int rc = grow(&eng->d_cmp_out, &eng->d_cmp_out_bytes, bytes);
+    if (rc) return rc;
+    d = (double*)eng->d_cmp_out;
+  }
+  PLA_HIP(pla::launch_bb_gamma_draws(seed, alpha, n_boot, n_obs, d, s));
+  eng->last_kernels = "bb_gamma_draws_kernel";
+  if (mem_space == PLA_DEVICE) return PLA_OK;
+  PLA_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
   return PLA_OK;
 }
 

@@ -125,6 +125,18 @@ hipError_t launch_waic_col(const void* in, int dtype, int64_t n_obs, int n_draws
 hipError_t launch_group_sum(const void* in, int dtype, int64_t stride_obs, int64_t row0, int64_t n_rows, int64_t n_src, bool blocked,
                             bool first_block, int n_draws, const int64_t* offsets, const int64_t* members, int64_t n_groups_total,
                             int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream);
+// model comparison (pla_compare.h): x is a (K, N) matrix of pointwise values, row k at x + k * pitch.  `part` is engine workspace:
+// compare_n_tiles(N) * (3K + 2) doubles (moments), * (K + 1) (stacking), nb * compare_n_tiles(N) * (K + 1) (bootstrap).  grid_cap > 0
+// caps the workgroups per launch (the results do not depend on it).
+int64_t compare_n_tiles(int64_t n_obs);
+hipError_t launch_compare_moments(const void* x, int dtype, int64_t pitch, int K, int64_t N, int best, double* part, double* out,
+                                  int grid_cap, hipStream_t stream);  // out [3K + 1]
+hipError_t launch_stacking_eval(const void* x, int dtype, int64_t pitch, int K, int64_t N, double scale_mul, const double* w,
+                                double* part, double* out, int grid_cap, hipStream_t stream);  // w [K] device; out [K + 1]: F, G
+// replicates [b0, b0 + nb): z rows 0 .. nb-1 of the launch (z points at replicate b0's row)
+hipError_t launch_bb_bootstrap(const void* x, int dtype, int64_t pitch, int K, int64_t N, double scale_mul, uint64_t seed, double alpha,
+                               int64_t b0, int64_t nb, double* part, double* z, int grid_cap, hipStream_t stream);
+hipError_t launch_bb_gamma_draws(uint64_t seed, double alpha, int64_t B, int64_t N, double* out, hipStream_t stream);
 // largest tail count the kernels accept
 int max_tail_count();
 

@@ -418,6 +418,90 @@ class Engine:
                                             out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # ------------------------------------------------------------------ model comparison
+    @staticmethod
+    def _compare_input(x):
+        """(matrix, pointer, dtype code, K, N, pitch, mem_space) of a (n_models, n_obs) matrix: rows with unit stride, a pitch
+        of at least n_obs (copied otherwise)."""
+        if _is_torch_tensor(x):
+            import torch
+
+            if x.dim() != 2 or not x.is_cuda:
+                raise ValueError("expected a 2-D (n_models, n_obs) CUDA tensor")
+            if x.dtype not in (torch.float64, torch.float32):
+                x = x.to(torch.float64)
+            K, N = x.shape
+            if (N > 1 and x.stride(1) != 1) or (K > 1 and x.stride(0) < N):
+                x = x.contiguous()
+            code = _capi.PLA_F64 if x.dtype == torch.float64 else _capi.PLA_F32
+            return x, C.c_void_p(x.data_ptr()), code, K, N, (x.stride(0) if K > 1 else N), PLA_DEVICE
+        a = np.asarray(x)
+        if a.dtype not in (np.float64, np.float32):
+            a = a.astype(np.float64)
+        if a.ndim != 2:
+            raise ValueError("expected a 2-D (n_models, n_obs) array")
+        K, N = a.shape
+        if (N > 1 and a.strides[1] != a.itemsize) or (K > 1 and (a.strides[0] % a.itemsize or a.strides[0] < N * a.itemsize)):
+            a = np.ascontiguousarray(a)
+        return a, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), K, N, (a.strides[0] // a.itemsize if K > 1 else N), PLA_HOST
+
+    def compare_moments(self, x, best):
+        """(n_models, n_obs) pointwise values -> ``out[3K + 1]`` (``pla_compare_moments``): ``out[3k]`` = sum of row k,
+        ``out[3k + 1]`` / ``out[3k + 2]`` = mean / M2 of ``x[k] - x[best]`` (dse = sqrt(M2)), ``out[3K]`` = sum of the column
+        maxima.  NumPy in -> ndarray; CUDA tensor in -> CUDA tensor (nothing synchronised)."""
+        x, ptr, code, K, N, pitch, mem = self._compare_input(x)
+        if mem == PLA_DEVICE:
+            import torch
+
+            out = torch.empty(3 * K + 1, dtype=torch.float64, device=x.device)
+            check(self._lib.pla_compare_moments(self._h, ptr, code, K, N, pitch, int(best), PLA_DEVICE, self._stream(),
+                                                C.c_void_p(out.data_ptr())))
+            return out
+        out = np.empty(3 * K + 1)
+        check(self._lib.pla_compare_moments(self._h, ptr, code, K, N, pitch, int(best), PLA_HOST, None, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def stacking_eval(self, x, weights, scale_mul=1.0):
+        """One evaluation of the stacking objective (``pla_stacking_eval``): returns ``(F, G)`` on the host, F = sum_i log d_i and
+        G[k] = sum_i e_ik / d_i with e_ik = exp(s x_ik - max_k s x_ik), d_i = sum_k w_k e_ik, s = ``scale_mul``."""
+        x, ptr, code, K, N, pitch, mem = self._compare_input(x)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != K:
+            raise ValueError(f"expected {K} weights, got {w.size}")
+        out = np.empty(K + 1)
+        check(self._lib.pla_stacking_eval(self._h, ptr, code, K, N, pitch, float(scale_mul), w.ctypes.data_as(C.c_void_p), mem,
+                                          self._stream() if mem == PLA_DEVICE else None, out.ctypes.data_as(C.c_void_p)))
+        return float(out[0]), out[1:].copy()
+
+    def bb_bootstrap(self, x, n_boot, alpha=1.0, seed=0, scale_mul=1.0):
+        """Bayesian-bootstrap replicates ``z`` (n_boot, n_models) of ``N * s * sum_i G_bi x_ik / sum_i G_bi`` with Gamma(alpha)
+        weights drawn in the kernel from the Philox stream keyed by ``seed`` (``pla_bb_bootstrap``).  NumPy in -> ndarray;
+        CUDA tensor in -> CUDA tensor (nothing synchronised)."""
+        x, ptr, code, K, N, pitch, mem = self._compare_input(x)
+        B = int(n_boot)
+        if mem == PLA_DEVICE:
+            import torch
+
+            z = torch.empty((B, K), dtype=torch.float64, device=x.device)
+            check(self._lib.pla_bb_bootstrap(self._h, ptr, code, K, N, pitch, float(scale_mul), B, float(alpha), int(seed) & (2**64 - 1),
+                                             PLA_DEVICE, self._stream(), C.c_void_p(z.data_ptr())))
+            return z
+        z = np.empty((B, K))
+        check(self._lib.pla_bb_bootstrap(self._h, ptr, code, K, N, pitch, float(scale_mul), B, float(alpha), int(seed) & (2**64 - 1),
+                                         PLA_HOST, None, z.ctypes.data_as(C.c_void_p)))
+        return z
+
+    def bb_gamma_draws(self, seed, alpha, n_boot, n_obs):
+        """The gamma stream of :meth:`bb_bootstrap` on its own (``pla_bb_gamma_draws``): (n_boot, n_obs) ndarray of G_bi."""
+        out = np.empty((int(n_boot), int(n_obs)))
+        check(self._lib.pla_bb_gamma_draws(self._h, int(seed) & (2**64 - 1), float(alpha), int(n_boot), int(n_obs), PLA_HOST, None,
+                                           out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_compare_grid(self, max_workgroups):
+        """Cap on the workgroups per launch of the comparison passes (0: the library's choice).  The results do not depend on it."""
+        check(self._lib.pla_engine_set_compare_grid(self._h, int(max_workgroups)))
+
     # ------------------------------------------------------------------ reductions
     def reduce_pointwise(self, diag, loo_i, lppd_i, good_k):
         if _is_torch_tensor(loo_i):
