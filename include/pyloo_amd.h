@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PLA_ABI_VERSION 6
+#define PLA_ABI_VERSION 7
 
 /* status codes */
 #define PLA_OK 0
@@ -293,6 +293,55 @@ int pla_bb_bootstrap(pla_engine *eng, const void *x, int dtype, int64_t n_models
 int pla_bb_gamma_draws(pla_engine *eng, uint64_t seed, double alpha, int64_t n_boot, int64_t n_obs, int mem_space,
                        void *stream, double *out);
 int pla_engine_set_compare_grid(pla_engine *eng, int max_workgroups);
+
+/*
+ * Non-factorised LOO -- loo_nonfactor's conditional log-likelihood for one joint multivariate normal or Student-t model
+ * (loo_nonfactor.py:466-557, and compute_beta_minus_i 686-733 in closed form).  For draw s, with C_s the given matrix, r = y - mu_s,
+ * P = C_s^-1, c_i = P_ii and g = P r:
+ *   PLA_MVN_NORMAL     ll_is = -log(2 pi)/2 + log(c_i)/2 - g_i^2 / (2 c_i)                                         (490-497)
+ *   PLA_MVN_STUDENT_T  with nu = df_s + N - 1 and beta_i = r'g - g_i^2 / c_i, sigma_i = (df_s + beta_i) / nu / c_i:
+ *                      ll_is = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi sigma_i)/2 - (nu+1)/2 log(1 + (g_i/c_i)^2 / (nu sigma_i))
+ *                                                                                                                 (498-557)
+ * The matrix is inverted whether it is a covariance or a precision matrix: the reference does so (478), and so does this call.
+ * Inputs: y [n_obs], mu (draw s at mu + s * mu_pitch), mat (draw s at mat + s * mat_pitch, each C-contiguous n_obs x n_obs), df
+ * [n_draws] (PLA_MVN_STUDENT_T only; may be NULL otherwise), all of `dtype` (PLA_F32 is promoted on load; all arithmetic is f64),
+ * all in `mem_space`.  Host inputs are staged to the device in blocks of draws of PLA_INGEST_BLOCK_MB (default 1 GiB).
+ * Outputs in `mem_space`: out_ll (ll of (i, s) at out_ll[i * ll_stride_obs + s * ll_stride_draw], f64; host calls need
+ * ll_stride_draw == 1; the LOO pass reads (n_obs, n_draws) with the draws fastest) and flags [n_draws] int32, the status of each draw:
+ *   PLA_NF_GENERAL          the general route (LU with partial pivoting) computed it
+ *   PLA_NF_SINGULAR         an exact zero pivot (numpy.linalg.inv's LinAlgError, 479-481): an all -inf row, no df check
+ *   PLA_NF_NONFINITE        a non-finite entry in the matrix, mu_s or y: an all -inf row (the reference's NaN inverse, 559-571)
+ *   PLA_NF_DF_NONPOS        df_s <= 0 (509-516): an all -inf row
+ *   PLA_NF_BETA_NONFINITE   some beta_i not finite (525-533): those entries -inf
+ *   PLA_NF_CLAMPED          some c_i <= 0, clamped to DBL_EPSILON (what 486-488 intends; the reference raises there instead)
+ * NaN log-likelihoods are returned as they are (the front replaces them with -inf, 559-571).
+ * Routes (pla_engine_set_nonfactor_route; csrc/pla_nonfactor.h): PLA_NF_ROUTE_AUTO (0): LDS for n_obs <= the LDS bound
+ * (pla_nonfactor_lds_max_obs), the blocked route above it (16-column panels, trailing updates on the f64 matrix cores);
+ * PLA_NF_ROUTE_LDS: the LDS route where n_obs allows it; PLA_NF_ROUTE_WORKSPACE: the blocked route; PLA_NF_ROUTE_GENERAL: every
+ * draw through LU.  The Cholesky routes leave draws that are not symmetric
+ * within 1e-12 relative or not numerically positive definite to the general route.  Every draw is computed by one workgroup in a
+ * fixed order: the output bits do not depend on the route grid (pla_engine_set_nonfactor_grid), the staging block, host vs device
+ * input, or f32 vs the same values as f64.  n_obs > PLA_NONFACTOR_MAX_OBS: PLA_ERR_UNSUPPORTED.
+ */
+#define PLA_NONFACTOR_MAX_OBS 1024
+#define PLA_MVN_NORMAL 0
+#define PLA_MVN_STUDENT_T 1
+#define PLA_NF_GENERAL 1
+#define PLA_NF_SINGULAR 2
+#define PLA_NF_NONFINITE 4
+#define PLA_NF_DF_NONPOS 8
+#define PLA_NF_BETA_NONFINITE 16
+#define PLA_NF_CLAMPED 32
+#define PLA_NF_ROUTE_AUTO 0
+#define PLA_NF_ROUTE_LDS 1
+#define PLA_NF_ROUTE_WORKSPACE 2
+#define PLA_NF_ROUTE_GENERAL 3
+int pla_nonfactor_loglik(pla_engine *eng, const void *y, const void *mu, const void *mat, const void *df, int dtype, int64_t n_obs,
+                         int64_t n_draws, int64_t mu_pitch, int64_t mat_pitch, int model_type, int mem_space, void *stream,
+                         double *out_ll, int64_t ll_stride_obs, int64_t ll_stride_draw, int32_t *flags);
+int pla_engine_set_nonfactor_route(pla_engine *eng, int route);
+int pla_engine_set_nonfactor_grid(pla_engine *eng, int max_workgroups);
+int pla_nonfactor_lds_max_obs(void);
 
 /* Timing of the dominant kernel, measured with hipEvents on the launch stream.
  * enable != 0 brackets every main-kernel launch with events; pla_engine_kernel_ms returns the

@@ -12,7 +12,12 @@ PLA_PSIS, PLA_SIS, PLA_TIS = 0, 1, 2
 METHOD_CODES = {"psis": PLA_PSIS, "sis": PLA_SIS, "tis": PLA_TIS}
 AGG_N, AGG_SUM_LOO, AGG_M2_LOO, AGG_SUM_LPPD, AGG_N_HIGH, AGG_N_NONFINITE, AGG_MIN_DIAG, AGG_N_SLOW = range(8)
 AGG_COUNT = 8
-ABI_VERSION = 6
+ABI_VERSION = 7
+PLA_MVN_NORMAL, PLA_MVN_STUDENT_T = 0, 1
+PLA_NONFACTOR_MAX_OBS = 1024
+# status word of a draw of pla_nonfactor_loglik
+NF_GENERAL, NF_SINGULAR, NF_NONFINITE, NF_DF_NONPOS, NF_BETA_NONFINITE, NF_CLAMPED = 1, 2, 4, 8, 16, 32
+NF_ROUTE_AUTO, NF_ROUTE_LDS, NF_ROUTE_WORKSPACE, NF_ROUTE_GENERAL = 0, 1, 2, 3
 
 # every symbol declared in include/pyloo_amd.h
 SYMBOLS = (
@@ -23,6 +28,7 @@ SYMBOLS = (
     "pla_engine_last_kernels", "pla_aggregate_pack", "pla_aggregate_merge", "pla_fill_synthetic_chains",
     "pla_env_overrides", "pla_engine_stream_stats", "pla_group_sum", "pla_psis_loo_groups",
     "pla_compare_moments", "pla_stacking_eval", "pla_bb_bootstrap", "pla_bb_gamma_draws", "pla_engine_set_compare_grid",
+    "pla_nonfactor_loglik", "pla_engine_set_nonfactor_route", "pla_engine_set_nonfactor_grid", "pla_nonfactor_lds_max_obs",
 )
 
 
@@ -92,6 +98,10 @@ def load_library():
     lib.pla_bb_bootstrap.argtypes = [vp, vp, ci, i64, i64, i64, dbl, i64, dbl, C.c_uint64, ci, vp, vp]
     lib.pla_bb_gamma_draws.argtypes = [vp, C.c_uint64, dbl, i64, i64, ci, vp, vp]
     lib.pla_engine_set_compare_grid.argtypes = [vp, ci]
+    lib.pla_nonfactor_loglik.argtypes = [vp, vp, vp, vp, vp, ci, i64, i64, i64, i64, ci, ci, vp, vp, i64, i64, vp]
+    lib.pla_engine_set_nonfactor_route.argtypes = [vp, ci]
+    lib.pla_engine_set_nonfactor_grid.argtypes = [vp, ci]
+    lib.pla_nonfactor_lds_max_obs.argtypes = []
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

@@ -13,6 +13,7 @@
 
 #include "../../include/pyloo_amd.h"
 #include "pla_launch.h"
+#include "pla_nonfactor.h"
 
 namespace {
 
@@ -84,6 +85,14 @@ struct pla_engine {
   void* d_cmp_out = nullptr;  // ... and the outputs of host calls / of the stacking evaluation
   size_t d_cmp_out_bytes = 0;
   int compare_grid = 0;  // pla_engine_set_compare_grid: workgroup cap of the comparison passes (0: the library's choice)
+  void* d_nf = nullptr;  // non-factorised LOO: slots of the blocked / general routes (pla_nonfactor.h)
+  size_t d_nf_bytes = 0;
+  void* d_nf_in = nullptr;  // ... staging of a host call: one block of draws (mu, matrices, df) and y
+  size_t d_nf_in_bytes = 0;
+  void* d_nf_out = nullptr;  // ... and its outputs (ll block, flags)
+  size_t d_nf_out_bytes = 0;
+  int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
+  int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
   // timing of the main kernel
   bool timing = false;
   static constexpr int kTimingRing = 64;  // launches timed without a host-side wait in between
@@ -343,6 +352,9 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_gidx) (void)hipFree(e->d_gidx);
   if (e->d_cmp) (void)hipFree(e->d_cmp);
   if (e->d_cmp_out) (void)hipFree(e->d_cmp_out);
+  if (e->d_nf) (void)hipFree(e->d_nf);
+  if (e->d_nf_in) (void)hipFree(e->d_nf_in);
+  if (e->d_nf_out) (void)hipFree(e->d_nf_out);
   for (int i = 0; i < pla_engine::kTimingRing; ++i) {
     if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]);
     if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]);
@@ -1718,4 +1730,147 @@ int pla_fill_synthetic(pla_engine* eng, void* ll_device, int dtype, int64_t n_ob
   return PLA_OK;
 }
 
+
+// ---- non-factorised LOO (loo_nonfactor.py:466-557) -------------------------------------------------------------------------------
+int pla_nonfactor_lds_max_obs(void) { return pla::nonfactor_lds_max_obs(); }
+
+int pla_engine_set_nonfactor_route(pla_engine* eng, int route) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (route < PLA_NF_ROUTE_AUTO || route > PLA_NF_ROUTE_GENERAL) return fail(PLA_ERR_ARG, "route must be 0 .. 3, got %d", route);
+  EngineCall call(eng);
+  eng->nonfactor_route = route;
+  return PLA_OK;
+}
+
+int pla_engine_set_nonfactor_grid(pla_engine* eng, int max_workgroups) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (max_workgroups < 0) return fail(PLA_ERR_ARG, "max_workgroups < 0");
+  EngineCall call(eng);
+  eng->nonfactor_grid = max_workgroups;
+  return PLA_OK;
+}
+
+// draws per staging block of a host call: PLA_INGEST_BLOCK_MB (default 1 GiB) of matrices
+static int64_t nonfactor_block_draws(int64_t n_obs, int64_t n_draws, size_t esz) {
+  static const size_t bytes = [] {
+    const char* e = getenv("PLA_INGEST_BLOCK_MB");
+    const long mb = e ? atol(e) : 0;
+    return mb > 0 ? (size_t)mb << 20 : (size_t)1 << 30;
+  }();
+  int64_t r = (int64_t)(bytes / ((size_t)n_obs * (size_t)n_obs * esz));
+  if (r < 1) r = 1;
+  return r < n_draws ? r : n_draws;
+}
+
+// slots of the blocked and general routes: the engine's cap, else up to 512 within 1 GiB
+static int nonfactor_slots(int64_t n_obs, int64_t n_draws, int grid_cap) {
+  int64_t slots = (int64_t)(((size_t)1 << 30) / ((size_t)pla::nonfactor_slot_doubles((int)n_obs) * sizeof(double)));
+  if (slots > 512) slots = 512;
+  if (grid_cap > 0 && slots > grid_cap) slots = grid_cap;
+  if (slots > n_draws) slots = n_draws;
+  return (int)(slots < 1 ? 1 : slots);
+}
+
+int pla_nonfactor_loglik(pla_engine* eng, const void* y, const void* mu, const void* mat, const void* df, int dtype, int64_t n_obs,
+                         int64_t n_draws, int64_t mu_pitch, int64_t mat_pitch, int model_type, int mem_space, void* stream,
+                         double* out_ll, int64_t ll_stride_obs, int64_t ll_stride_draw, int32_t* flags) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (model_type != PLA_MVN_NORMAL && model_type != PLA_MVN_STUDENT_T) return fail(PLA_ERR_ARG, "bad model_type %d", model_type);
+  if (!y || !mu || !mat || !out_ll || !flags) return fail(PLA_ERR_ARG, "y / mu / mat / out_ll / flags is NULL");
+  if (model_type == PLA_MVN_STUDENT_T && !df) return fail(PLA_ERR_ARG, "df is NULL for a Student-t model");
+  if (n_obs < 1 || n_draws < 1) return fail(PLA_ERR_ARG, "n_obs and n_draws must be at least 1");
+  if (n_obs > PLA_NONFACTOR_MAX_OBS)
+    return fail(PLA_ERR_UNSUPPORTED, "n_obs = %lld exceeds the device limit of %d observations", (long long)n_obs,
+                PLA_NONFACTOR_MAX_OBS);
+  if (n_draws >= ((int64_t)1 << 31)) return fail(PLA_ERR_ARG, "n_draws must be below 2^31");
+  if ((n_draws > 1 && mu_pitch < n_obs) || (n_draws > 1 && mat_pitch < n_obs * n_obs))
+    return fail(PLA_ERR_ARG, "mu_pitch / mat_pitch smaller than one draw");
+  if (ll_stride_obs < 0 || ll_stride_draw < 0 || ll_stride_obs > INT32_MAX || ll_stride_draw > INT32_MAX)
+    return fail(PLA_ERR_ARG, "ll_stride_obs / ll_stride_draw must lie in [0, 2^31)");
+  if (mem_space == PLA_HOST && ll_stride_draw != 1 && n_draws > 1) return fail(PLA_ERR_ARG, "host calls need ll_stride_draw == 1");
+  if (mem_space == PLA_HOST && n_obs > 1 && ll_stride_obs < n_draws) return fail(PLA_ERR_ARG, "ll_stride_obs < n_draws");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int N = (int)n_obs;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int route = pla::nonfactor_route_for(N, eng->nonfactor_route);
+  const int64_t nb = mem_space == PLA_DEVICE ? n_draws : nonfactor_block_draws(n_obs, n_draws, esz);
+  const int slots = nonfactor_slots(n_obs, nb, eng->nonfactor_grid);
+  int rc = grow(&eng->d_nf, &eng->d_nf_bytes, (size_t)slots * (size_t)pla::nonfactor_slot_doubles(N) * sizeof(double));
+  if (rc) return rc;
+  pla::NonfactorParams p{};
+  p.N = N;
+  p.model = model_type;
+  p.ws = (double*)eng->d_nf;
+  p.slot = (int)pla::nonfactor_slot_doubles(N);
+  const char* kname = route == PLA_NF_ROUTE_LDS ? "nonfactor_lds_kernel<" : route == PLA_NF_ROUTE_WORKSPACE ? "nonfactor_blocked_kernel<" : "";
+  eng->last_kernels = std::string(kname) + (*kname ? std::string(pla::dtype_name(dtype)) + "> + " : std::string()) + "nonfactor_lu_kernel<" +
+                      pla::dtype_name(dtype) + ">" + (route == PLA_NF_ROUTE_GENERAL ? " (every draw)" : " (declined draws)") +
+                      (mem_space == PLA_DEVICE ? " (inputs read in place)" : " (inputs staged)");
+  if (mem_space == PLA_DEVICE) {
+    p.y = y;
+    p.mu = mu;
+    p.mat = mat;
+    p.df = df;
+    p.n_draws = (int)n_draws;
+    p.mu_pitch = n_draws > 1 ? mu_pitch : n_obs;
+    p.mat_pitch = n_draws > 1 ? mat_pitch : n_obs * n_obs;
+    p.out = out_ll;
+    p.so = ll_stride_obs;
+    p.sd = ll_stride_draw;
+    p.flags = flags;
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_nonfactor(p, dtype, route, slots, eng->nonfactor_grid, s));
+    return PLA_OK;
+  }
+  // host: blocks of nb draws through the staging buffers (C-contiguous: mu [nb][N], matrices [nb][N][N], df [nb], y [N])
+  const size_t in_elems = (size_t)nb * N * N + (size_t)nb * N + (size_t)nb + (size_t)N;
+  rc = grow(&eng->d_nf_in, &eng->d_nf_in_bytes, in_elems * esz);
+  if (rc) return rc;
+  rc = grow(&eng->d_nf_out, &eng->d_nf_out_bytes, (size_t)nb * N * sizeof(double) + (size_t)nb * sizeof(int32_t));
+  if (rc) return rc;
+  char* din = (char*)eng->d_nf_in;
+  void* dmat = din;
+  void* dmu = din + (size_t)nb * N * N * esz;
+  void* ddf = din + ((size_t)nb * N * N + (size_t)nb * N) * esz;
+  void* dy = din + ((size_t)nb * N * N + (size_t)nb * N + (size_t)nb) * esz;
+  double* dll = (double*)eng->d_nf_out;
+  int32_t* dfl = (int32_t*)(dll + (size_t)nb * N);
+  PLA_HIP(hipMemcpyAsync(dy, y, (size_t)N * esz, hipMemcpyHostToDevice, s));
+  for (int64_t b0 = 0; b0 < n_draws; b0 += nb) {
+    const int64_t n = n_draws - b0 < nb ? n_draws - b0 : nb;
+    const char* hmat = (const char*)mat + (size_t)b0 * (size_t)mat_pitch * esz;
+    const char* hmu = (const char*)mu + (size_t)b0 * (size_t)mu_pitch * esz;
+    const size_t row = (size_t)N * N * esz;
+    PLA_HIP(hipMemcpy2DAsync(dmat, row, hmat, (size_t)(n > 1 ? mat_pitch : (int64_t)N * N) * esz, row, (size_t)n,
+                             hipMemcpyHostToDevice, s));
+    PLA_HIP(hipMemcpy2DAsync(dmu, (size_t)N * esz, hmu, (size_t)(n > 1 ? mu_pitch : N) * esz, (size_t)N * esz, (size_t)n,
+                             hipMemcpyHostToDevice, s));
+    if (model_type == PLA_MVN_STUDENT_T)
+      PLA_HIP(hipMemcpyAsync(ddf, (const char*)df + (size_t)b0 * esz, (size_t)n * esz, hipMemcpyHostToDevice, s));
+    p.y = dy;
+    p.mu = dmu;
+    p.mat = dmat;
+    p.df = model_type == PLA_MVN_STUDENT_T ? ddf : nullptr;
+    p.n_draws = (int)n;
+    p.mu_pitch = N;
+    p.mat_pitch = (int64_t)N * N;
+    p.out = dll;
+    p.so = n;
+    p.sd = 1;
+    p.flags = dfl;
+    {
+      TimedLaunch t(eng, s);
+      PLA_HIP(pla::launch_nonfactor(p, dtype, route, slots, eng->nonfactor_grid, s));
+    }
+    PLA_HIP(hipMemcpy2DAsync(out_ll + b0, (size_t)(N > 1 ? ll_stride_obs : n_draws) * sizeof(double), dll, (size_t)n * sizeof(double),
+                             (size_t)n * sizeof(double), (size_t)N, hipMemcpyDeviceToHost, s));
+    PLA_HIP(hipMemcpyAsync(flags + b0, dfl, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+  }
+  return PLA_OK;
+}
 }  // extern "C"

@@ -137,6 +137,15 @@ hipError_t launch_stacking_eval(const void* x, int dtype, int64_t pitch, int K, 
 hipError_t launch_bb_bootstrap(const void* x, int dtype, int64_t pitch, int K, int64_t N, double scale_mul, uint64_t seed, double alpha,
                                int64_t b0, int64_t nb, double* part, double* z, int grid_cap, hipStream_t stream);
 hipError_t launch_bb_gamma_draws(uint64_t seed, double alpha, int64_t B, int64_t N, double* out, hipStream_t stream);
+// non-factorised LOO (pla_nonfactor.h): the (N, S) conditional log-likelihood of one block of draws.  `route` is
+// nonfactor_route_for(N, engine setting); p.ws holds ws_slots slots of p.slot = nonfactor_slot_doubles(N) doubles (the blocked
+// and general kernels take one slot per workgroup); grid_cap > 0 caps the LDS kernel's workgroups (the results do not depend on
+// either).
+struct NonfactorParams;
+int nonfactor_lds_max_obs();
+int64_t nonfactor_slot_doubles(int n_obs);
+int nonfactor_route_for(int n_obs, int forced);
+hipError_t launch_nonfactor(const NonfactorParams& p, int dtype, int route, int ws_slots, int grid_cap, hipStream_t stream);
 // largest tail count the kernels accept
 int max_tail_count();
 

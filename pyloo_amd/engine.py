@@ -502,6 +502,55 @@ class Engine:
         """Cap on the workgroups per launch of the comparison passes (0: the library's choice).  The results do not depend on it."""
         check(self._lib.pla_engine_set_compare_grid(self._h, int(max_workgroups)))
 
+    # ------------------------------------------------------------------ non-factorised LOO
+    def nonfactor_log_lik(self, y, mu, mat, df=None, model="normal"):
+        """Conditional log-likelihood of a joint multivariate normal / Student-t model (``pla_nonfactor_loglik``).
+
+        ``y`` (N,), ``mu`` (S, N), ``mat`` (S, N, N) -- one covariance matrix per draw, inverted whatever it holds, as the
+        reference does --, ``df`` (S,) for ``model="student_t"``.  NumPy arrays (staged by the library in blocks of draws) or
+        CUDA tensors (read in place; non-contiguous ones are made contiguous once).  Mixed f32 / f64 inputs are all taken as
+        f64.  Returns ``(ll, flags)``: ``ll`` (N, S) float64 with the draws fastest, ``flags`` (S,) int32 status words
+        (``PLA_NF_*``); CUDA tensors when any input is one (nothing synchronised), ndarrays otherwise (CPU tensors included)."""
+        code = {"normal": _capi.PLA_MVN_NORMAL, "student_t": _capi.PLA_MVN_STUDENT_T}[model]
+        arrays = [y, mu, mat] + ([df] if code == _capi.PLA_MVN_STUDENT_T else [])
+        if any(_is_torch_tensor(a) and a.is_cuda for a in arrays):
+            import torch
+
+            dev = next(a.device for a in arrays if _is_torch_tensor(a) and a.is_cuda)  # (CPU tensors are copied to it)
+            f64 = not all(a.dtype == torch.float32 if _is_torch_tensor(a) else np.asarray(a).dtype == np.float32 for a in arrays)
+            dt = torch.float64 if f64 else torch.float32
+            arrays = [(a if _is_torch_tensor(a) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=dt).contiguous() for a in arrays]
+            yt, mut, matt = arrays[:3]
+            S, N = mut.shape
+            ll = torch.empty((N, S), dtype=torch.float64, device=dev)
+            flags = torch.empty(S, dtype=torch.int32, device=dev)
+            dfp = C.c_void_p(arrays[3].data_ptr()) if len(arrays) > 3 else None
+            check(self._lib.pla_nonfactor_loglik(self._h, C.c_void_p(yt.data_ptr()), C.c_void_p(mut.data_ptr()),
+                                                 C.c_void_p(matt.data_ptr()), dfp, _capi.PLA_F64 if f64 else _capi.PLA_F32, N, S, N,
+                                                 N * N, code, PLA_DEVICE, self._stream(), C.c_void_p(ll.data_ptr()), S, 1,
+                                                 C.c_void_p(flags.data_ptr())))
+            return ll, flags
+        # host memory -- NumPy arrays and CPU tensors -- goes through the library's staging (PLA_HOST)
+        arrays = [a.detach().numpy() if _is_torch_tensor(a) else np.asarray(a) for a in arrays]
+        dt = np.float32 if all(a.dtype == np.float32 for a in arrays) else np.float64
+        arrays = [np.ascontiguousarray(a, dtype=dt) for a in arrays]
+        ya, mua, mata = arrays[:3]
+        S, N = mua.shape
+        ll = np.empty((N, S))
+        flags = np.empty(S, dtype=np.int32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        check(self._lib.pla_nonfactor_loglik(self._h, p(ya), p(mua), p(mata), p(arrays[3]) if len(arrays) > 3 else None,
+                                             dtype_code(np.dtype(dt)), N, S, N, N * N, code, PLA_HOST, None, p(ll), S, 1, p(flags)))
+        return ll, flags
+
+    def set_nonfactor_route(self, route):
+        """0: automatic; 1 / 2 / 3: the LDS, blocked (engine-memory) or general route wherever the shape allows it (tests)."""
+        check(self._lib.pla_engine_set_nonfactor_route(self._h, int(route)))
+
+    def set_nonfactor_grid(self, max_workgroups):
+        """Cap on the workgroups of the non-factorised LOO kernels (0: the library's choice).  The results do not depend on it."""
+        check(self._lib.pla_engine_set_nonfactor_grid(self._h, int(max_workgroups)))
+
     # ------------------------------------------------------------------ reductions
     def reduce_pointwise(self, diag, loo_i, lppd_i, good_k):
         if _is_torch_tensor(loo_i):
