@@ -217,6 +217,43 @@ int pla_psis_loo_groups(pla_engine *eng, const void *ll, int dtype, int64_t n_ob
                         double *logo_i, double *lppd_i, double *agg, int64_t *n_replaced);
 
 /*
+ * pla_gather_draws / pla_psis_loo_draws -- PSIS-LOO for draws of an approximate posterior (loo_approximate_posterior.py:223-348):
+ * the matrix with its draws taken in the order and multiplicity of an index (the importance-resampled draws, line 263), and the
+ * PSIS / SIS / TIS pass of pla_psis_loo over that matrix, without the matrix ever being materialised whole.
+ *
+ *   ll, n_obs, n_draws, strides   the matrix, as in pla_psis_loo.  Device matrices: any positive strides (draws contiguous with rows
+ *                 of at most pla_gather_lds_max_draws(dtype) draws are staged row by row in LDS and read once; observations
+ *                 contiguous goes through an LDS tile; everything else is gathered straight from global memory).  Host matrices:
+ *                 draws contiguous or observations contiguous, uploaded block by block and gathered on the device.
+ *   draw_index [n_out]  int64, in the memory space of `ll`; repeats allowed, 1 <= n_out <= 2^30, n_out need not equal n_draws.  Host
+ *                 lists are checked (entries in [0, n_draws): PLA_ERR_ARG); device lists are clamped into range on the device.
+ *   NaN entries   count as -1e10 in the dtype of ll (loo_approximate_posterior.py:223-232) and are counted in *n_replaced (memory
+ *                 space of ll; may be NULL): the number of NaN entries of ll[:, draw_index].  +-inf are not replaced.
+ *   pla_gather_draws     out (n_obs, n_out) C-contiguous, dtype of ll, in the memory space of ll
+ *   pla_psis_loo_draws   diag / loo_i / lppd_i [n_obs] double (each may be NULL), agg [PLA_AGG_COUNT] as pla_psis_loo's; tail_count
+ *                 refers to n_out.  Blocks of observations (sized like the ingest staging: PLA_INGEST_BLOCK_MB on the device) are
+ *                 gathered into the engine's staging buffer, each block's pass writes its slices, the aggregates are reduced once
+ *                 at the end.  Everything is enqueued on the caller's stream; once the workspace is sized nothing is allocated, so
+ *                 the device call can be captured after pla_engine_set_frozen.
+ *   contract      pla_gather_draws is bitwise ll[:, draw_index] (NaN replaced); the pointwise outputs of pla_psis_loo_draws are
+ *                 bitwise those of pla_psis_loo on that matrix uploaded draws-fastest, the aggregates agree to 1e-12 relative
+ *                 (another reduction order).  The results do not depend on the block size, on host or device input, or on the
+ *                 layout of ll.
+ *   pla_gather_lds_max_draws   the longest row (n_draws) the LDS route takes for a dtype (PLA_F64 / PLA_F32)
+ */
+int pla_gather_draws(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws,
+                     int64_t stride_obs, int64_t stride_draw, const int64_t *draw_index, int64_t n_out,
+                     int mem_space, void *stream, void *out, int64_t *n_replaced /* may be NULL */);
+
+int pla_psis_loo_draws(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws,
+                       int64_t stride_obs, int64_t stride_draw, const int64_t *draw_index, int64_t n_out,
+                       int method, int64_t tail_count, double scale_value, double good_k, int mem_space,
+                       void *stream, double *diag, double *loo_i, double *lppd_i, double *agg,
+                       int64_t *n_replaced);
+
+int pla_gather_lds_max_draws(int dtype);
+
+/*
  * pla_e_loo -- PSIS-weighted expectations of a same-shape matrix and their function-specific Pareto k.
  * Replaces, per observation, e_loo.py:214-236: `_normalize_log_weights` + `_compute_weighted_mean` (430-437, 557-559),
  * `_compute_weighted_variance` / `_wvar_func` (440-459, 518-531; sd = sqrt(variance), 462-465) and `compute_pareto_k` ->

@@ -29,6 +29,7 @@ SYMBOLS = (
     "pla_env_overrides", "pla_engine_stream_stats", "pla_group_sum", "pla_psis_loo_groups",
     "pla_compare_moments", "pla_stacking_eval", "pla_bb_bootstrap", "pla_bb_gamma_draws", "pla_engine_set_compare_grid",
     "pla_nonfactor_loglik", "pla_engine_set_nonfactor_route", "pla_engine_set_nonfactor_grid", "pla_nonfactor_lds_max_obs",
+    "pla_gather_draws", "pla_psis_loo_draws", "pla_gather_lds_max_draws",
 )
 
 
@@ -102,6 +103,9 @@ def load_library():
     lib.pla_engine_set_nonfactor_route.argtypes = [vp, ci]
     lib.pla_engine_set_nonfactor_grid.argtypes = [vp, ci]
     lib.pla_nonfactor_lds_max_obs.argtypes = []
+    lib.pla_gather_draws.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, vp, vp, vp]
+    lib.pla_psis_loo_draws.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, i64, dbl, dbl, ci, vp, vp, vp, vp, vp, vp]
+    lib.pla_gather_lds_max_draws.argtypes = [ci]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

@@ -1140,6 +1140,204 @@ int pla_psis_loo_groups(pla_engine* eng, const void* ll, int dtype, int64_t n_ob
   return PLA_OK;
 }
 
+// ---- approximate posteriors (loo_approximate_posterior.py:223-348) -------------------------------------------------------------
+// Draw index: draw_index[n_out] in the memory space of the matrix.  Host lists are checked here; device lists are clamped by the
+// gather kernel (pla_draws.h).
+static int check_draws(const int64_t* draw_index, int64_t n_out, int64_t n_draws, int mem_space) {
+  if (n_out < 1 || n_out > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_out out of range");
+  if (!draw_index) return fail(PLA_ERR_ARG, "draw_index is NULL");
+  if (mem_space == PLA_HOST)
+    for (int64_t j = 0; j < n_out; ++j)
+      if (draw_index[j] < 0 || draw_index[j] >= n_draws)
+        return fail(PLA_ERR_ARG, "draw_index[%lld] = %lld is outside [0, %lld)", (long long)j, (long long)draw_index[j], (long long)n_draws);
+  return PLA_OK;
+}
+
+static bool host_obs_fastest(int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw) {
+  return n_obs > 1 && n_draws > 1 && stride_obs == 1 && stride_draw >= n_obs;
+}
+
+// Device index lists are used as they are; host lists go up to the engine buffer behind the replaced-entry counter (word 0).
+static int draw_index_on_device(pla_engine* eng, const int64_t* draw_index, int64_t n_out, int mem_space, hipStream_t s,
+                                const int64_t** d_idx, unsigned long long** d_count) {
+  if (mem_space == PLA_DEVICE) {
+    *d_idx = draw_index;
+    *d_count = nullptr;
+    return PLA_OK;
+  }
+  int rc = grow(&eng->d_gidx, &eng->d_gidx_bytes, (size_t)(1 + n_out) * sizeof(int64_t));
+  if (rc) return rc;
+  int64_t* d = (int64_t*)eng->d_gidx;
+  PLA_HIP(hipMemsetAsync(d, 0, sizeof(int64_t), s));
+  PLA_HIP(hipMemcpyAsync(d + 1, draw_index, (size_t)n_out * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  *d_idx = d + 1;
+  *d_count = (unsigned long long*)d;
+  return PLA_OK;
+}
+
+// Rows [r0, r0 + nr) of the matrix with their draws gathered into `dst` (device, (nr, n_out) C-contiguous).  Device matrices are
+// read in place; a block of a host matrix goes up to the slab buffer as it lies -- (nr, n_draws) rows, or the (n_draws, nr) slab
+// of an observations-fastest matrix -- and is gathered from there.
+static int gather_block(pla_engine* eng, const void* ll, int dtype, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                        const int64_t* d_idx, int64_t n_out, int64_t r0, int64_t nr, int mem_space, hipStream_t s, void* dst,
+                        unsigned long long* d_count, const char** route) {
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  if (mem_space == PLA_DEVICE) {
+    PLA_HIP(pla::launch_gather_draws((const char*)ll + (size_t)r0 * (size_t)stride_obs * esz, dtype, stride_obs, stride_draw, nr,
+                                     (int)n_draws, d_idx, (int)n_out, dst, d_count, s, route));
+    return PLA_OK;
+  }
+  if (stride_draw == 1) {
+    const size_t row_bytes = (size_t)n_draws * esz;
+    PLA_HIP(hipMemcpy2DAsync(eng->d_slab, row_bytes, (const char*)ll + (size_t)r0 * (size_t)stride_obs * esz, (size_t)stride_obs * esz,
+                             row_bytes, (size_t)nr, hipMemcpyHostToDevice, s));
+    PLA_HIP(pla::launch_gather_draws(eng->d_slab, dtype, n_draws, 1, nr, (int)n_draws, d_idx, (int)n_out, dst, d_count, s, route));
+  } else {
+    PLA_HIP(hipMemcpy2DAsync(eng->d_slab, (size_t)nr * esz, (const char*)ll + (size_t)r0 * esz, (size_t)stride_draw * esz,
+                             (size_t)nr * esz, (size_t)n_draws, hipMemcpyHostToDevice, s));
+    PLA_HIP(pla::launch_gather_draws(eng->d_slab, dtype, 1, nr, nr, (int)n_draws, d_idx, (int)n_out, dst, d_count, s, route));
+  }
+  return PLA_OK;
+}
+
+static int check_gather(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                        int64_t stride_draw, const int64_t* draw_index, int64_t n_out, int mem_space) {
+  int rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, PLA_SIS, 0, mem_space);
+  if (rc) return rc;
+  rc = check_draws(draw_index, n_out, n_draws, mem_space);
+  if (rc) return rc;
+  if (mem_space == PLA_HOST && stride_draw != 1 && !host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw))
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST input needs unit stride along the draws, or along the observations");
+  return PLA_OK;
+}
+
+// rows per block of a host call: the slab holds n_draws, the staging n_out entries per row
+static int64_t host_gather_rows(int64_t n_obs, int64_t n_draws, int64_t n_out, size_t esz) {
+  return staged_chunk_rows(PLA_HOST, false, n_obs, n_draws > n_out ? n_draws : n_out, esz);
+}
+
+int pla_gather_draws(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                     const int64_t* draw_index, int64_t n_out, int mem_space, void* stream, void* out, int64_t* n_replaced) {
+  int rc = check_gather(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, draw_index, n_out, mem_space);
+  if (rc) return rc;
+  if (n_obs > 0 && !out) return fail(PLA_ERR_ARG, "out is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int64_t* d_idx = nullptr;
+  unsigned long long* d_count = nullptr;
+  rc = draw_index_on_device(eng, draw_index, n_out, mem_space, s, &d_idx, &d_count);
+  if (rc) return rc;
+  const char* route = "";
+  if (mem_space == PLA_DEVICE) {
+    if (n_replaced) PLA_HIP(hipMemsetAsync(n_replaced, 0, sizeof(int64_t), s));
+    TimedLaunch t(eng, s);  // (the gather kernel's own time: pla_engine_kernel_ms)
+    rc = gather_block(eng, ll, dtype, n_draws, stride_obs, stride_draw, d_idx, n_out, 0, n_obs, mem_space, s, out,
+                      (unsigned long long*)n_replaced, &route);
+    eng->last_kernels = std::string(route) + " (matrix read in place)";
+    return rc;
+  }
+  const int64_t rows = host_gather_rows(n_obs, n_draws, n_out, esz);
+  rc = grow(&eng->d_slab, &eng->d_slab_bytes, (size_t)rows * (size_t)n_draws * esz);
+  if (rc) return rc;
+  rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)rows * (size_t)n_out * esz);
+  if (rc) return rc;
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+    const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+    rc = gather_block(eng, ll, dtype, n_draws, stride_obs, stride_draw, d_idx, n_out, r0, nr, mem_space, s, eng->d_in, d_count, &route);
+    if (rc) return rc;
+    PLA_HIP(hipMemcpyAsync((char*)out + (size_t)r0 * (size_t)n_out * esz, eng->d_in, (size_t)nr * (size_t)n_out * esz,
+                           hipMemcpyDeviceToHost, s));
+    PLA_HIP(hipStreamSynchronize(s));  // the buffers are reused by the next block
+  }
+  eng->last_kernels = std::string(route) + " (blocks of observations uploaded)";
+  unsigned long long h = 0;
+  if (n_replaced) PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
+}
+
+int pla_psis_loo_draws(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                       int64_t stride_draw, const int64_t* draw_index, int64_t n_out, int method, int64_t tail_count, double scale_value,
+                       double good_k, int mem_space, void* stream, double* diag, double* loo_i, double* lppd_i, double* agg,
+                       int64_t* n_replaced) {
+  int rc = check_gather(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, draw_index, n_out, mem_space);
+  if (rc) return rc;
+  rc = check_common(eng, ll, dtype, n_obs, n_out, n_out, 1, method, tail_count, mem_space);  // the pass runs over n_out draws
+  if (rc) return rc;
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int64_t* d_idx = nullptr;
+  unsigned long long* d_count = nullptr;
+  rc = draw_index_on_device(eng, draw_index, n_out, mem_space, s, &d_idx, &d_count);
+  if (rc) return rc;
+  if (mem_space == PLA_DEVICE) {
+    d_count = (unsigned long long*)n_replaced;
+    if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+  }
+  // pointwise outputs: the caller's device vectors, else (host calls, or agg without them) the engine scratch
+  double *dd = diag, *dl = loo_i, *dp = lppd_i;
+  if (mem_space == PLA_HOST || (agg && (!dd || !dl || !dp))) {
+    size_t have_b = eng->d_pw_elems * sizeof(double);
+    rc = grow((void**)&eng->d_pw, &have_b, (size_t)(3 * n_obs + PLA_AGG_COUNT) * sizeof(double));
+    eng->d_pw_elems = have_b / sizeof(double);
+    if (rc) return rc;
+    if (mem_space == PLA_HOST || !dd) dd = eng->d_pw;
+    if (mem_space == PLA_HOST || !dl) dl = eng->d_pw + n_obs;
+    if (mem_space == PLA_HOST || !dp) dp = eng->d_pw + 2 * n_obs;
+  }
+  // one block of observations at a time: its gathered rows in the bounded staging buffer, the PSIS / SIS / TIS pass over them into
+  // its slices
+  const int64_t rows = mem_space == PLA_DEVICE ? staged_chunk_rows(mem_space, true, n_obs, n_out, esz) : host_gather_rows(n_obs, n_draws, n_out, esz);
+  if (mem_space == PLA_HOST) {
+    rc = grow(&eng->d_slab, &eng->d_slab_bytes, (size_t)rows * (size_t)n_draws * esz);
+    if (rc) return rc;
+  }
+  rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)rows * (size_t)n_out * esz);
+  if (rc) return rc;
+  // (every block's pass zeroes the slow-row total it reports: the blocks' totals are summed beside it and put back for the reduction)
+  unsigned long long* block_total = eng->counters + pla::kCounterBlockTotal;
+  PLA_HIP(hipMemsetAsync(block_total, 0, sizeof(unsigned long long), s));
+  std::string label;
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+    const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+    const char* route = "";
+    rc = gather_block(eng, ll, dtype, n_draws, stride_obs, stride_draw, d_idx, n_out, r0, nr, mem_space, s, eng->d_in, d_count, &route);
+    if (rc) return rc;
+    rc = psis_loo_run(eng, eng->d_in, dtype, nr, nullptr, nr, n_out, n_out, 1, method, tail_count, scale_value, good_k, PLA_DEVICE, stream,
+                      dd ? dd + r0 : nullptr, dl ? dl + r0 : nullptr, dp ? dp + r0 : nullptr, nullptr);
+    if (rc) return rc;
+    PLA_HIP(pla::launch_add_counter(eng->counters + 1, block_total, s));
+    if (r0 == 0) label = std::string(route) + " per block of observations, then " + eng->last_kernels;
+    if (mem_space == PLA_HOST) PLA_HIP(hipStreamSynchronize(s));  // the buffers are reused by the next block
+  }
+  eng->last_kernels = label;
+  // the aggregates once, over all observations
+  double* dagg = mem_space == PLA_HOST ? eng->d_pw + 3 * n_obs : agg;
+  if (agg) {
+    pla::ReduceParams rp{dd, dl, dp, n_obs, good_k, dagg, block_total};
+    PLA_HIP(pla::launch_reduce(rp, eng->d_red, s));
+  }
+  if (mem_space == PLA_DEVICE) return PLA_OK;
+  if (n_obs > 0) {
+    if (diag) PLA_HIP(hipMemcpyAsync(diag, dd, n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (loo_i) PLA_HIP(hipMemcpyAsync(loo_i, dl, n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (lppd_i) PLA_HIP(hipMemcpyAsync(lppd_i, dp, n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (agg) PLA_HIP(hipMemcpyAsync(agg, dagg, PLA_AGG_COUNT * sizeof(double), hipMemcpyDeviceToHost, s));
+  unsigned long long h = 0;
+  if (n_replaced) PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
+}
+
+int pla_gather_lds_max_draws(int dtype) { return pla::gather_lds_max_draws(dtype); }
+
 // ---- model comparison (compare.py:205-229, 477-577) ----------------------------------------------------------------------------
 static int compare_check(pla_engine* eng, const void* x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch, int mem_space) {
   if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");

@@ -125,6 +125,15 @@ hipError_t launch_waic_col(const void* in, int dtype, int64_t n_obs, int n_draws
 hipError_t launch_group_sum(const void* in, int dtype, int64_t stride_obs, int64_t row0, int64_t n_rows, int64_t n_src, bool blocked,
                             bool first_block, int n_draws, const int64_t* offsets, const int64_t* members, int64_t n_groups_total,
                             int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream);
+// draw gather of the approximate-posterior pass (pla_draws.h): out[i, j] = in[i * stride_obs + clamp(draw_index[j]) * stride_draw] for
+// the n_rows rows at `in`, out a contiguous (n_rows, n_out) block; NaN -> -1e10, counted in `replaced` (may be null).  *route (may be
+// null): text for pla_engine_last_kernels.  Rows of at most gather_lds_max_draws(dtype) draws are staged in LDS.
+int gather_lds_max_draws(int dtype);
+hipError_t launch_gather_draws(const void* in, int dtype, int64_t stride_obs, int64_t stride_draw, int64_t n_rows, int n_draws,
+                               const int64_t* draw_index, int n_out, void* out, unsigned long long* replaced, hipStream_t stream,
+                               const char** route);
+// *total += *value (one lane; the slow-row total of one block of a pla_psis_loo_draws call into the call's total)
+hipError_t launch_add_counter(const unsigned long long* value, unsigned long long* total, hipStream_t stream);
 // model comparison (pla_compare.h): x is a (K, N) matrix of pointwise values, row k at x + k * pitch.  `part` is engine workspace:
 // compare_n_tiles(N) * (3K + 2) doubles (moments), * (K + 1) (stacking), nb * compare_n_tiles(N) * (K + 1) (bootstrap).  grid_cap > 0
 // caps the workgroups per launch (the results do not depend on it).

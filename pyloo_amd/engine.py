@@ -276,6 +276,108 @@ class Engine:
                                             p(logo_i), p(lppd_i), p(agg), C.byref(nrep)))
         return {"diag": diag, "logo_i": logo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": int(nrep.value)}
 
+    # ------------------------------------------------------------------ approximate posteriors: draws through an index
+    @staticmethod
+    def _host_draws(draw_index, n_draws):
+        """Draw index as contiguous int64, range-checked like :meth:`_host_rows` (no negative wrap-around)."""
+        idx = np.ascontiguousarray(np.asarray(draw_index).reshape(-1), dtype=np.int64)
+        if idx.size == 0:
+            raise ValueError("draw_index is empty")
+        if idx.min() < 0 or idx.max() >= n_draws:
+            raise IndexError(f"draw indices must lie in [0, {n_draws}), got range [{idx.min()}, {idx.max()}]")
+        return idx
+
+    def _device_draws(self, draw_index, n_draws, device):
+        import torch
+
+        if _is_torch_tensor(draw_index) and draw_index.is_cuda:  # used as it is: the kernel clamps, the caller vouches for the range
+            idx = draw_index.to(device=device, dtype=torch.int64).contiguous().reshape(-1)
+            if idx.numel() == 0:
+                raise ValueError("draw_index is empty")
+            return idx
+        if _is_torch_tensor(draw_index):
+            draw_index = draw_index.numpy()
+        return torch.from_numpy(self._host_draws(draw_index, n_draws)).to(device)
+
+    @staticmethod
+    def _draws_input(ll):
+        import torch
+
+        if ll.dim() != 2 or not ll.is_cuda:
+            raise ValueError("expected a 2-D CUDA tensor")
+        if ll.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"unsupported dtype {ll.dtype}")
+        return ll  # (every strided view is read in place: pla_gather_draws takes any positive strides)
+
+    def gather_draws(self, ll, draw_index, out=None):
+        """(n_obs, n_draws) matrix + draw index -> ``(matrix, n_replaced)`` (``pla_gather_draws``): bitwise ``ll[:, draw_index]`` in
+        the matrix's dtype, draws contiguous, NaN written as -1e10 and counted.  NumPy in -> ``(ndarray, int)``; CUDA tensor in ->
+        ``(tensor, int64 tensor of one element)``, nothing synchronised.  ``out``: a contiguous CUDA tensor to write into."""
+        if _is_torch_tensor(ll):
+            import torch
+
+            t = self._draws_input(ll)
+            n, s = t.shape
+            idx = self._device_draws(draw_index, s, t.device)
+            m = idx.numel()
+            if out is None:
+                out = torch.empty((n, m), dtype=t.dtype, device=t.device)
+            elif tuple(out.shape) != (n, m) or out.dtype != t.dtype or not out.is_contiguous() or out.device != t.device:
+                raise ValueError("out must be a contiguous tensor of shape (n_obs, len(draw_index)) with the matrix's dtype and device")
+            nrep = torch.zeros(1, dtype=torch.int64, device=t.device)
+            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            check(self._lib.pla_gather_draws(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
+                                             C.c_void_p(idx.data_ptr()), m, PLA_DEVICE, self._stream(), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(nrep.data_ptr())))
+            return out, nrep
+        a = self._as_2d_host(ll, allow_obs_fastest=True)
+        n, s = a.shape
+        so, sd = self._host_strides(a)
+        idx = self._host_draws(draw_index, s)
+        res = np.empty((n, idx.size), dtype=a.dtype)
+        nrep = C.c_int64(0)
+        check(self._lib.pla_gather_draws(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd,
+                                         idx.ctypes.data_as(C.c_void_p), idx.size, PLA_HOST, None, res.ctypes.data_as(C.c_void_p),
+                                         C.byref(nrep)))
+        return res, int(nrep.value)
+
+    def psis_loo_draws(self, ll, draw_index, tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True):
+        """PSIS / SIS / TIS pass over ``ll[:, draw_index]`` (``pla_psis_loo_draws``) without materialising that matrix: blocks of
+        observations are gathered into the bounded staging buffer and passed on.  ``tail_count`` refers to ``len(draw_index)``.
+
+        Returns ``dict(diag, loo_i, lppd_i, agg, n_replaced)`` -- NumPy arrays (and an int) for NumPy input, CUDA tensors for
+        CUDA-tensor input (nothing synchronised)."""
+        mcode = METHOD_CODES[method]
+        if _is_torch_tensor(ll):
+            import torch
+
+            t = self._draws_input(ll)
+            n, s = t.shape
+            dev = t.device
+            idx = self._device_draws(draw_index, s, dev)
+            mk = lambda: torch.empty(n, dtype=torch.float64, device=dev)  # noqa: E731
+            diag, loo_i, lppd_i = (mk(), mk(), mk()) if (pointwise or aggregate) else (None, None, None)
+            agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev) if aggregate else None
+            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
+            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            check(self._lib.pla_psis_loo_draws(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1), p(idx),
+                                               idx.numel(), mcode, int(tail_count), float(scale_value), float(good_k), PLA_DEVICE,
+                                               self._stream(), p(diag), p(loo_i), p(lppd_i), p(agg), p(nrep)))
+            return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": nrep}
+        a = self._as_2d_host(ll, allow_obs_fastest=True)
+        n, s = a.shape
+        so, sd = self._host_strides(a)
+        idx = self._host_draws(draw_index, s)
+        diag, loo_i, lppd_i = (np.empty(n), np.empty(n), np.empty(n)) if pointwise else (None, None, None)
+        agg = np.zeros(AGG_COUNT) if aggregate else None
+        nrep = C.c_int64(0)
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        check(self._lib.pla_psis_loo_draws(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd, p(idx), idx.size,
+                                           mcode, int(tail_count), float(scale_value), float(good_k), PLA_HOST, None, p(diag),
+                                           p(loo_i), p(lppd_i), p(agg), C.byref(nrep)))
+        return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": int(nrep.value)}
+
     # ------------------------------------------------------------------ weights pass
     def importance_weights(self, logw, tail_count=0, method="psis"):
         """(n_obs, n_draws) log ratios -> (lw, diag) (``pla_importance_weights``)."""
