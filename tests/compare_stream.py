@@ -1,8 +1,12 @@
 """NumPy restatement of the model-comparison kernels (csrc/pla_compare.h), for the tests.
 
-``philox4x32_10`` and ``gamma_draws`` restate the bootstrap's gamma stream operation by operation; ``bb_z`` its replicates.
+``philox4x32_10`` and ``gamma_draws`` restate the bootstrap's gamma stream operation by operation; ``bb_z`` its replicates
+(all of them, or the ones named by ``replicates=``).  ``moments_reference`` and ``stacking_reference`` are the moments and the
+stacking pass in wider arithmetic (``math.fsum`` and ``np.longdouble``), to judge the kernels' f64 results against.
 ``NumpyCompareEngine`` answers the Engine methods that ``pyloo_amd.compare`` calls, so the CPU suite can run the front without
 a GPU.  TEST INFRASTRUCTURE ONLY."""
+
+import math
 
 import numpy as np
 
@@ -27,9 +31,20 @@ def u53(hi, lo):
     return ((v >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0**-53
 
 
-def gamma_draws(seed, alpha, B, N):
-    """G[b, i] of the stream specified in csrc/pla_compare.h."""
-    b, i = np.meshgrid(np.arange(B, dtype=np.uint64), np.arange(N, dtype=np.uint64), indexing="ij")
+def _replicate_numbers(B, replicates):
+    if replicates is None:
+        return np.arange(B, dtype=np.uint64)
+    reps = np.asarray(replicates, dtype=np.int64).reshape(-1)
+    if reps.size and (reps.min() < 0 or reps.max() >= B):
+        raise ValueError(f"replicates must lie in [0, {B})")
+    return reps.astype(np.uint64)
+
+
+def gamma_draws(seed, alpha, B, N, replicates=None):
+    """G[b, i] of the stream specified in csrc/pla_compare.h, for b < B; with ``replicates`` (an array of replicate numbers
+    below B) only those rows, in the order given: the stream is a function of (seed, alpha, b, i), so they are the bits of the
+    same rows of the full call."""
+    b, i = np.meshgrid(_replicate_numbers(B, replicates), np.arange(N, dtype=np.uint64), indexing="ij")
     key = (np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32))
     zero, one = np.zeros_like(b), np.ones_like(b)
     if alpha == 1.0:
@@ -59,10 +74,16 @@ def gamma_draws(seed, alpha, B, N):
     return g
 
 
-def bb_z(x, B, alpha, seed, scale_mul=1.0):
-    """z[b, k] = N * scale_mul * (sum_i G_bi x_ki / sum_i G_bi)."""
+def bb_z(x, B, alpha, seed, scale_mul=1.0, replicates=None):
+    """z[b, k] = N * scale_mul * (sum_i G_bi x_ki / sum_i G_bi), for b < B or for the rows ``replicates`` alone."""
     x = np.asarray(x, dtype=np.float64)
-    G = gamma_draws(seed, alpha, B, x.shape[1])
+    return bb_z_from_gammas(gamma_draws(seed, alpha, B, x.shape[1], replicates), x, scale_mul)
+
+
+def bb_z_from_gammas(G, x, scale_mul=1.0):
+    """``bb_z`` for gamma draws ``G`` (rows of ``gamma_draws``) that the caller holds: they depend on (seed, alpha, b, i) alone,
+    so tests of several matrices of one width generate them once."""
+    x = np.asarray(x, dtype=np.float64)
     return (x.shape[1] * scale_mul) * ((G @ x.T) / G.sum(axis=1, keepdims=True))
 
 
@@ -71,6 +92,31 @@ def stacking_objective(x, w, scale_mul=1.0):
     xs = scale_mul * np.asarray(x, dtype=np.float64).T
     e = np.exp(xs - xs.max(axis=1, keepdims=True))
     return -np.sum(np.log(e @ np.asarray(w)))
+
+
+def moments_reference(x, best):
+    """``out[3K + 1]`` of ``compare_moments`` in wider arithmetic, as ``np.longdouble``: the row sums and the sum of the column
+    maxima by ``math.fsum`` (exactly rounded), the mean and the two-pass M2 of ``d = x[k] - x[best]`` in ``np.longdouble``.
+    f32 input is widened first (exactly): the kernels promote on load, so this is the arithmetic on the f32 values."""
+    x = np.asarray(x).astype(np.float64)
+    K, N = x.shape
+    xl = x.astype(np.longdouble)
+    out = np.zeros(3 * K + 1, dtype=np.longdouble)
+    for k in range(K):
+        d = xl[k] - xl[best]
+        mean = d.sum() / np.longdouble(N)
+        out[3 * k], out[3 * k + 1], out[3 * k + 2] = math.fsum(x[k]), mean, np.sum((d - mean) ** 2)
+    out[3 * K] = math.fsum(x.max(axis=0))
+    return out
+
+
+def stacking_reference(x, w, scale_mul=1.0):
+    """``(F, G)`` of ``stacking_eval`` in ``np.longdouble``: F = sum_i log d_i, G[k] = sum_i e_ik / d_i with
+    e_ik = exp(s x_ik - max_k s x_ik), d_i = sum_k w_k e_ik.  f32 input is widened first (exactly)."""
+    xs = np.longdouble(scale_mul) * np.asarray(x).astype(np.float64).astype(np.longdouble).T
+    e = np.exp(xs - xs.max(axis=1, keepdims=True))
+    d = e @ np.asarray(w, dtype=np.float64).astype(np.longdouble)
+    return np.sum(np.log(d)), (e / d[:, None]).sum(axis=0)
 
 
 class NumpyCompareEngine:

@@ -16,7 +16,8 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from compare_cases import CASES, pointwise  # noqa: E402
-from compare_stream import NumpyCompareEngine, gamma_draws, philox4x32_10, stacking_objective  # noqa: E402
+from compare_stream import (NumpyCompareEngine, bb_z, gamma_draws, moments_reference, philox4x32_10, stacking_objective,  # noqa: E402
+                            stacking_reference)
 
 GOLD = np.load(os.path.join(HERE, "golden", "compare.npz"))
 
@@ -73,6 +74,41 @@ def test_gamma_stream_is_a_function_of_its_coordinates():
     b = gamma_draws(5, 0.5, 10, 20)
     assert np.array_equal(a, b[:6, :9])
     assert not np.array_equal(a, gamma_draws(6, 0.5, 6, 9))
+
+
+@pytest.mark.parametrize("alpha", [1.0, 0.5, 2.0])
+def test_replicate_subset_is_the_same_rows_of_the_full_call(alpha):
+    """``replicates=`` restates a few replicates of a long vector: bitwise the rows of the full call, in the order asked for."""
+    reps = np.array([0, 63, 64, 7, 129])
+    full = gamma_draws(91, alpha, 130, 301)
+    assert np.array_equal(gamma_draws(91, alpha, 130, 301, replicates=reps), full[reps])
+    x = pointwise(2, 3, 301, "log")
+    assert np.array_equal(bb_z(x, 130, alpha, 91, -0.5, replicates=reps), bb_z(x, 130, alpha, 91, -0.5)[reps])
+    assert gamma_draws(91, alpha, 130, 301, replicates=[]).shape == (0, 301)
+    with pytest.raises(ValueError, match="replicates"):
+        gamma_draws(91, alpha, 130, 301, replicates=[130])
+
+
+def test_wider_references_agree_with_the_f64_restatement():
+    """``moments_reference`` / ``stacking_reference`` (fsum, longdouble) against the plain f64 NumPy engine, on well-conditioned
+    input; f32 input is the arithmetic on the widened f32 values."""
+    eng = NumpyCompareEngine()
+    x = pointwise(4, 5, 777, "deviance")
+    w = np.array([0.1, 0.3, 0.2, 0.15, 0.25])
+    for xx in (x, x.astype(np.float32)):
+        ref = moments_reference(xx, 3)
+        assert ref.dtype == np.longdouble and ref[3 * 3 + 1] == 0 and ref[3 * 3 + 2] == 0
+        np.testing.assert_allclose(ref.astype(float), eng.compare_moments(xx.astype(np.float64), 3), rtol=1e-12, atol=1e-13)
+        F, G = stacking_reference(xx, w, -0.5)
+        F64, G64 = eng.stacking_eval(xx.astype(np.float64), w, -0.5)
+        assert abs(float(F) - F64) <= 1e-12 * abs(F64)
+        np.testing.assert_allclose(G.astype(float), G64, rtol=1e-12)
+    # two-pass in longdouble holds where a one-pass sum of squares in f64 has lost everything
+    rng = np.random.default_rng(0)
+    noise = rng.normal(size=5000)
+    y = np.stack([np.zeros(5000), 1e6 + 1e-3 * noise])
+    m2 = float(moments_reference(y, 0)[3 + 2])
+    assert abs(m2 / (1e-6 * np.sum((noise - noise.mean()) ** 2)) - 1) < 1e-6
 
 
 # ---- the front ----------------------------------------------------------------------------------------------------------------
