@@ -254,6 +254,48 @@ int pla_psis_loo_draws(pla_engine *eng, const void *ll, int dtype, int64_t n_obs
 int pla_gather_lds_max_draws(int dtype);
 
 /*
+ * pla_kfold_lme / pla_kfold_reduce -- K-fold cross-validation from per-fold log-likelihoods (loo_kfold.py:250-299, 643-692): the
+ * log mean exp of every held-out observation under its own fold's draws and of every observation under the full fit in ONE
+ * ragged pass over the resident matrices, and the pointwise values, sums and standard-error moments behind it.  The refits are
+ * the caller's.
+ *
+ * pla_kfold_lme
+ *   sources       n_sources matrices of one dtype in DEVICE memory, described by parallel HOST arrays (uploaded by the call, 40
+ *                 bytes a source): src_base[k], src_rows[k], src_draws[k] (1 .. 2^30), src_stride_row[k] >= 0 and
+ *                 src_stride_draw[k] > 0 in elements.  Source 0 is the full fit by convention: with nan_flag != 0 its NaN entries
+ *                 count as -1e10 (loo_kfold.py:250-259) and are counted in *n_replaced (device, zeroed by the call; may be NULL).
+ *                 Nothing else is replaced anywhere: a NaN, a +inf or a row of -inf give NaN, as utils.py:344-357 does.
+ *   tasks         source_offsets [n_sources + 1], task_row [n_tasks], task_out [n_tasks]: int64 in DEVICE memory.  Tasks
+ *                 [source_offsets[k], source_offsets[k + 1]) belong to source k; task t writes
+ *                     out[task_out[t]] = logsumexp_s(ll_k[task_row[t], :]) - log(src_draws[k])          (f32 reduced in f64)
+ *                 task_row is clamped into the source, a task_out outside [0, n_out) is dropped.
+ *   routes        per source: unit draw stride, 16-byte aligned rows, at most 4096 draws -> a wavefront per task, the row in
+ *                 registers; unit row stride (observations fastest) -> a lane per task; anything else -> a workgroup per task.
+ *                 One launch per route present, whatever n_sources is; pla_engine_last_kernels names them.
+ *   mem_space     PLA_DEVICE.  PLA_HOST returns PLA_ERR_UNSUPPORTED (the Python engine uploads).
+ * pla_kfold_reduce   elpd [n_obs] (held-out), lpd_full [n_obs], n_replaced (may be NULL): device.  Writes p_i = lpd_full - elpd and
+ *                 kfold_i = scale * elpd ([n_obs] each, may be NULL) and agg [PLA_AGG_COUNT], the slots of pla_psis_loo reused:
+ *                     [PLA_AGG_N] n_obs, [PLA_AGG_SUM_LOO] sum kfold_i, [PLA_AGG_M2_LOO] sum (kfold_i - mean)^2,
+ *                     [PLA_AGG_SUM_LPPD] sum p_i, [PLA_AGG_N_HIGH] sum (p_i - mean)^2, [PLA_AGG_N_NONFINITE] *n_replaced, others 0
+ *                 (both M2 two-pass about the mean, as np.var: se = sqrt(M2)).  The observations are cut into tiles whose width
+ *                 depends on n_obs alone and the partials are combined in a fixed order: the same input gives the same bits
+ *                 whatever the grid (pla_engine_set_compare_grid caps it).
+ * Everything is enqueued on the caller's stream.  pla_kfold_lme keeps the table in two pinned host buffers used in turn: a call
+ * waits on the host for the table upload of the call BEFORE THE PREVIOUS ONE (done long ago unless two calls are still queued), and
+ * the first two calls, or a larger table, allocate pinned memory (not allowed once the engine is frozen).  pla_engine_last_kernels
+ * also states how many kernels the ragged pass launched.
+ */
+int pla_kfold_lme(pla_engine *eng, const void *const *src_base, const int64_t *src_rows, const int64_t *src_draws,
+                  const int64_t *src_stride_row, const int64_t *src_stride_draw, int64_t n_sources, int dtype,
+                  int nan_flag, const int64_t *source_offsets, const int64_t *task_row, const int64_t *task_out,
+                  int64_t n_tasks, int mem_space, void *stream, double *out, int64_t n_out,
+                  int64_t *n_replaced /* may be NULL */);
+
+int pla_kfold_reduce(pla_engine *eng, const double *elpd, const double *lpd_full, int64_t n_obs, double scale,
+                     const int64_t *n_replaced /* may be NULL */, int mem_space, void *stream, double *p_i,
+                     double *kfold_i, double *agg);
+
+/*
  * pla_e_loo -- PSIS-weighted expectations of a same-shape matrix and their function-specific Pareto k.
  * Replaces, per observation, e_loo.py:214-236: `_normalize_log_weights` + `_compute_weighted_mean` (430-437, 557-559),
  * `_compute_weighted_variance` / `_wvar_func` (440-459, 518-531; sd = sqrt(variance), 462-465) and `compute_pareto_k` ->

@@ -30,6 +30,7 @@ SYMBOLS = (
     "pla_compare_moments", "pla_stacking_eval", "pla_bb_bootstrap", "pla_bb_gamma_draws", "pla_engine_set_compare_grid",
     "pla_nonfactor_loglik", "pla_engine_set_nonfactor_route", "pla_engine_set_nonfactor_grid", "pla_nonfactor_lds_max_obs",
     "pla_gather_draws", "pla_psis_loo_draws", "pla_gather_lds_max_draws",
+    "pla_kfold_lme", "pla_kfold_reduce",
 )
 
 
@@ -106,6 +107,8 @@ def load_library():
     lib.pla_gather_draws.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, vp, vp, vp]
     lib.pla_psis_loo_draws.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, i64, dbl, dbl, ci, vp, vp, vp, vp, vp, vp]
     lib.pla_gather_lds_max_draws.argtypes = [ci]
+    lib.pla_kfold_lme.argtypes = [vp, vp, vp, vp, vp, vp, i64, ci, ci, vp, vp, vp, i64, ci, vp, vp, i64, vp]
+    lib.pla_kfold_reduce.argtypes = [vp, vp, vp, i64, dbl, vp, ci, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

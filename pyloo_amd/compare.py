@@ -14,8 +14,8 @@ pointwise values of the K models are stacked into one (K, N) matrix -- on the de
 
 Deviations: the Bayesian bootstrap draws from a specified Philox4x32-10 stream (csrc/pla_compare.h), not from NumPy's
 ``RandomState`` Dirichlet stream, so its weights agree with the reference statistically, not bit for bit.  As in the reference,
-an ``int`` seed also seeds NumPy's global generator (``np.random.seed(seed)``, compare.py:548-549).  ``ic="kfold"`` needs the PyMC
-wrapper and raises ``NotImplementedError``.  The input dictionary is copied shallowly (the reference deep-copies it; nothing
+an ``int`` seed also seeds NumPy's global generator (``np.random.seed(seed)``, compare.py:548-549).  ``ic="kfold"`` on anything
+but precomputed ``ELPDData`` (of ``loo_kfold``) needs the refits and raises ``NotImplementedError``.  The input dictionary is copied shallowly (the reference deep-copies it; nothing
 here modifies it).
 """
 
@@ -210,7 +210,7 @@ def _calculate_ics(compare_dict, scale=None, ic=None, var_name=None, observation
         if isinstance(dataset, ELPDData):
             continue
         if ic == "kfold":
-            raise NotImplementedError("ic='kfold' (loo_kfold) needs the PyMC wrapper; outside the scope of pyloo_amd")
+            raise NotImplementedError("ic='kfold' needs the refits of every model: compute them with loo_kfold(..., pointwise=True) and pass the ELPDData")
         try:
             if ic == "waic":
                 compare_dict[name] = waic(dataset, pointwise=True, var_name=var_name, scale=scale)

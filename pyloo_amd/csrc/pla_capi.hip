@@ -91,6 +91,15 @@ struct pla_engine {
   size_t d_nf_in_bytes = 0;
   void* d_nf_out = nullptr;  // ... and its outputs (ll block, flags)
   size_t d_nf_out_bytes = 0;
+  void* d_kf = nullptr;  // k-fold: the source table of the last pla_kfold_lme call ...
+  size_t d_kf_bytes = 0;
+  // ... its pinned host copy (the upload reads it after the call has returned), two of them used in turn, and the event behind
+  // each upload: a call waits for the upload of the call before the previous one before it rewrites that copy
+  void* h_kf[2] = {nullptr, nullptr};
+  size_t h_kf_bytes[2] = {0, 0};
+  hipEvent_t kf_event[2] = {nullptr, nullptr};
+  int kf_turn = 0;
+  std::string kf_label;  // the routes of the last pla_kfold_lme, for the text pla_kfold_reduce leaves in last_kernels
   int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
   int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
   // timing of the main kernel
@@ -355,6 +364,11 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_nf) (void)hipFree(e->d_nf);
   if (e->d_nf_in) (void)hipFree(e->d_nf_in);
   if (e->d_nf_out) (void)hipFree(e->d_nf_out);
+  if (e->d_kf) (void)hipFree(e->d_kf);
+  for (int i = 0; i < 2; ++i) {
+    if (e->h_kf[i]) (void)hipHostFree(e->h_kf[i]);
+    if (e->kf_event[i]) (void)hipEventDestroy(e->kf_event[i]);
+  }
   for (int i = 0; i < pla_engine::kTimingRing; ++i) {
     if (e->ev0[i]) (void)hipEventDestroy(e->ev0[i]);
     if (e->ev1[i]) (void)hipEventDestroy(e->ev1[i]);
@@ -1337,6 +1351,101 @@ int pla_psis_loo_draws(pla_engine* eng, const void* ll, int dtype, int64_t n_obs
 }
 
 int pla_gather_lds_max_draws(int dtype) { return pla::gather_lds_max_draws(dtype); }
+
+// ---- k-fold cross-validation (loo_kfold.py:250-299, 643-692) -------------------------------------------------------------------
+int pla_kfold_lme(pla_engine* eng, const void* const* src_base, const int64_t* src_rows, const int64_t* src_draws,
+                  const int64_t* src_stride_row, const int64_t* src_stride_draw, int64_t n_sources, int dtype, int nan_flag,
+                  const int64_t* source_offsets, const int64_t* task_row, const int64_t* task_out, int64_t n_tasks, int mem_space,
+                  void* stream, double* out, int64_t n_out, int64_t* n_replaced) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (mem_space == PLA_HOST) return fail(PLA_ERR_UNSUPPORTED, "pla_kfold_lme reads device memory only (upload the fold matrices first)");
+  if (n_sources < 1 || n_sources > (int64_t)1 << 24) return fail(PLA_ERR_ARG, "n_sources out of range");
+  if (!src_base || !src_rows || !src_draws || !src_stride_row || !src_stride_draw) return fail(PLA_ERR_ARG, "a source array is NULL");
+  if (n_tasks < 0 || n_out < 0) return fail(PLA_ERR_ARG, "n_tasks < 0 or n_out < 0");
+  if (n_tasks > 0 && (!source_offsets || !task_row || !task_out || !out)) return fail(PLA_ERR_ARG, "a task array or out is NULL");
+  for (int64_t k = 0; k < n_sources; ++k) {
+    if (src_rows[k] < 0) return fail(PLA_ERR_ARG, "source %lld: n_rows < 0", (long long)k);
+    if (src_rows[k] > 0 && !src_base[k]) return fail(PLA_ERR_ARG, "source %lld: base pointer is NULL", (long long)k);
+    if (src_draws[k] < 1 || src_draws[k] > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "source %lld: n_draws out of range", (long long)k);
+    if (src_stride_row[k] < 0 || src_stride_draw[k] <= 0) return fail(PLA_ERR_ARG, "source %lld: bad strides", (long long)k);
+  }
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_replaced) PLA_HIP(hipMemsetAsync(n_replaced, 0, sizeof(int64_t), s));
+  if (n_tasks == 0) return PLA_OK;
+  // the table: built in pinned host memory that outlives the call, uploaded on the caller's stream
+  const size_t bytes = (size_t)n_sources * sizeof(pla::KfoldSource);
+  int rc = grow(&eng->d_kf, &eng->d_kf_bytes, bytes);
+  if (rc) return rc;
+  const int turn = eng->kf_turn;
+  eng->kf_turn ^= 1;
+  if (!eng->kf_event[turn]) {
+    if (g_frozen) return fail(PLA_ERR_FROZEN, "the engine is frozen and has no k-fold table yet");
+    PLA_HIP(hipEventCreateWithFlags(&eng->kf_event[turn], hipEventDisableTiming));
+  } else {
+    PLA_HIP(hipEventSynchronize(eng->kf_event[turn]));  // (the upload of two calls ago: done, unless that call is still queued)
+  }
+  if (eng->h_kf_bytes[turn] < bytes) {
+    if (g_frozen) return fail(PLA_ERR_FROZEN, "the engine workspace is frozen and this call needs a larger k-fold table");
+    if (eng->h_kf[turn]) (void)hipHostFree(eng->h_kf[turn]);
+    eng->h_kf[turn] = nullptr;
+    eng->h_kf_bytes[turn] = 0;
+    PLA_HIP(hipHostMalloc(&eng->h_kf[turn], bytes, hipHostMallocDefault));
+    eng->h_kf_bytes[turn] = bytes;
+  }
+  pla::KfoldSource* tab = (pla::KfoldSource*)eng->h_kf[turn];
+  unsigned routes = 0;
+  for (int64_t k = 0; k < n_sources; ++k) {
+    // (a source without rows has no tasks: its entry only has to be harmless)
+    const int route = pla::kfold_route(src_base[k], dtype, src_stride_row[k], src_stride_draw[k], src_draws[k]);
+    tab[k] = pla::KfoldSource{src_base[k], src_rows[k], src_stride_row[k], src_stride_draw[k], (int)src_draws[k],
+                              route | ((k == 0 && nan_flag) ? pla::kKfoldNanFlag : 0)};
+    if (src_rows[k] > 0) routes |= 1u << route;
+  }
+  PLA_HIP(hipMemcpyAsync(eng->d_kf, tab, bytes, hipMemcpyHostToDevice, s));
+  PLA_HIP(hipEventRecord(eng->kf_event[turn], s));
+  pla::KfoldParams p{(const pla::KfoldSource*)eng->d_kf, (int)n_sources, source_offsets, task_row, task_out, n_tasks, out, n_out,
+                     (unsigned long long*)n_replaced};
+  int launches = 0;
+  {
+    TimedLaunch t(eng, s);  // (the ragged pass alone: pla_engine_kernel_ms)
+    PLA_HIP(pla::launch_kfold_lme(p, dtype, routes, s, &launches));
+  }
+  std::string label;
+  for (int r = 0; r < 3; ++r)
+    if (routes & (1u << r)) label += std::string(label.empty() ? "" : " + ") + pla::kfold_route_name(r) + "<" + pla::dtype_name(dtype) + ">";
+  // (the count is of the launches made, not of the routes asked for)
+  eng->kf_label = label + " (matrices read in place; " + std::to_string(launches) + (launches == 1 ? " launch)" : " launches)");
+  eng->last_kernels = eng->kf_label;
+  return PLA_OK;
+}
+
+int pla_kfold_reduce(pla_engine* eng, const double* elpd, const double* lpd_full, int64_t n_obs, double scale, const int64_t* n_replaced,
+                     int mem_space, void* stream, double* p_i, double* kfold_i, double* agg) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (mem_space == PLA_HOST) return fail(PLA_ERR_UNSUPPORTED, "pla_kfold_reduce reads device memory only");
+  if (n_obs < 1 || n_obs >= ((int64_t)1 << 40)) return fail(PLA_ERR_ARG, "n_obs must lie in [1, 2^40), got %lld", (long long)n_obs);
+  if (!elpd || !lpd_full || !agg) return fail(PLA_ERR_ARG, "elpd, lpd_full or agg is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc = grow(&eng->d_cmp, &eng->d_cmp_bytes, (size_t)pla::kfold_n_tiles(n_obs) * 4 * sizeof(double));
+  if (rc) return rc;
+  {
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_kfold_reduce(elpd, lpd_full, n_obs, scale, p_i, kfold_i, (double*)eng->d_cmp,
+                                     (const unsigned long long*)n_replaced, agg, eng->compare_grid, s));
+  }
+  // (behind pla_kfold_lme the text keeps the routes of the ragged pass)
+  const std::string finish = "kfold_tiles_kernel<0> + kfold_tiles_kernel<1> + kfold_final_kernel";
+  eng->last_kernels = eng->kf_label.empty() ? finish : eng->kf_label + ", then " + finish;
+  eng->kf_label.clear();
+  return PLA_OK;
+}
 
 // ---- model comparison (compare.py:205-229, 477-577) ----------------------------------------------------------------------------
 static int compare_check(pla_engine* eng, const void* x, int dtype, int64_t n_models, int64_t n_obs, int64_t pitch, int mem_space) {

@@ -155,6 +155,38 @@ int nonfactor_lds_max_obs();
 int64_t nonfactor_slot_doubles(int n_obs);
 int nonfactor_route_for(int n_obs, int forced);
 hipError_t launch_nonfactor(const NonfactorParams& p, int dtype, int route, int ws_slots, int grid_cap, hipStream_t stream);
+// k-fold cross-validation (pla_kfold.h).  The ragged log-mean-exp: a device table of sources and a task list grouped by source.
+enum KfoldRoute { kKfoldWave = 0, kKfoldLane = 1, kKfoldBlock = 2 };
+constexpr int kKfoldRouteMask = 3, kKfoldNanFlag = 4;
+
+struct KfoldSource {  // one entry of the device table
+  const void* base;
+  int64_t n_rows;
+  int64_t stride_row, stride_draw;  // elements
+  int n_draws;
+  int flags;  // route | kKfoldNanFlag
+};
+
+struct KfoldParams {
+  const KfoldSource* src;  // [n_sources] device
+  int n_sources;
+  const int64_t* source_offsets;  // [n_sources + 1] device
+  const int64_t* task_row;        // [n_tasks]
+  const int64_t* task_out;        // [n_tasks]
+  int64_t n_tasks;
+  double* out;
+  int64_t n_out;
+  unsigned long long* replaced;  // [1] device counter (may be null)
+};
+
+// the route of a source (its strides, length and alignment decide), the ragged pass (one launch per route in `routes`, a bit mask of
+// 1 << route) and the finishing pass (part: kfold_n_tiles(N) * 4 doubles of engine workspace; grid_cap > 0 caps the workgroups)
+int kfold_route(const void* base, int dtype, int64_t stride_row, int64_t stride_draw, int64_t n_draws);
+hipError_t launch_kfold_lme(const KfoldParams& p, int dtype, unsigned routes, hipStream_t stream, int* launches);  // *launches: kernels launched
+const char* kfold_route_name(int route);
+int64_t kfold_n_tiles(int64_t n_obs);
+hipError_t launch_kfold_reduce(const double* elpd, const double* lpd_full, int64_t n_obs, double scale, double* p_i, double* kfold_i,
+                               double* part, const unsigned long long* replaced, double* agg, int grid_cap, hipStream_t stream);
 // largest tail count the kernels accept
 int max_tail_count();
 

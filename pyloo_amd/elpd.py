@@ -2,7 +2,7 @@
 
 Mirrors the LOO part of the reference container (pyloo/elpd.py:100-498): same index keys,
 same properties, same printed report (README.md:76-84 of the reference; the LOGO report of elpd.py:165-220), including the Pareto-k
-table with bins ``(-inf, good_k], (good_k, 1], (1, inf)`` (elpd.py:300-330).  The k-fold,
+table with bins ``(-inf, good_k], (good_k, 1], (1, inf)`` (elpd.py:300-330), and the k-fold report (elpd.py:64-72, 130-163).  The
 sub-sampling and non-factorised report variants are out of scope.
 """
 
@@ -35,6 +35,16 @@ elpd_logo   {elpd:<8.2f}    {se:<.2f}
 p_logo       {p_logo:<8.2f}    {p_logo_se:<.2f}
 logoic      {logoic:<8.2f}    {logoic_se:<.2f}"""
 
+_KFOLD_REPORT = """
+Computed from {n_samples} posterior samples using {K}-fold cross-validation
+with {n_points} observations.{stratify_msg}
+
+           Estimate       SE
+elpd_kfold   {elpd:<8.2f}    {se:<.2f}
+p_kfold       {p_kfold:<8.2f}    {p_kfold_se:<.2f}
+kfoldic      {kfoldic:<8.2f}    {kfoldic_se:<.2f}
+"""
+
 _K_TABLE = """
 ------
 
@@ -56,7 +66,7 @@ _WARNED = "\n\nThere has been a warning during the calculation. Please check the
 class ELPDData(pd.Series):
     """Expected-log-pointwise-predictive-density results with a friendly ``print``."""
 
-    _metadata = ["_method"]
+    _metadata = ["_method", "_K", "_stratified", "_grouped"]
 
     @property
     def _constructor(self):  # keep the subclass through pandas operations
@@ -72,6 +82,13 @@ class ELPDData(pd.Series):
             return text + (_WARNED if self.warning else "")
         if kind == "logo":
             return self._logo_report()
+        if kind == "kfold":
+            # elpd.py:130-163 (kfoldic is printed as -2 elpd_kfold whatever the scale, as the reference does)
+            text = _KFOLD_REPORT.format(n_samples=self.n_samples, K=self.K, n_points=self.n_data_points, elpd=self["elpd_kfold"],
+                                        se=self["se"], p_kfold=self["p_kfold"], p_kfold_se=self["p_kfold_se"],
+                                        kfoldic=-2 * self["elpd_kfold"], kfoldic_se=2 * self["se"],
+                                        stratify_msg=" Using stratified k-fold cross-validation" if self.stratified else "")
+            return text + (_WARNED if self.warning else "")
         if kind != "loo":
             raise ValueError("Invalid ELPDData object")
         tail = ""
@@ -141,3 +158,28 @@ class ELPDData(pd.Series):
     @method.setter
     def method(self, value):
         object.__setattr__(self, "_method", value)
+
+    @property
+    def K(self):
+        """Number of folds of a k-fold result."""
+        return getattr(self, "_K", None)
+
+    @K.setter
+    def K(self, value):
+        object.__setattr__(self, "_K", value)
+
+    @property
+    def stratified(self):
+        return getattr(self, "_stratified", False)
+
+    @stratified.setter
+    def stratified(self, value):
+        object.__setattr__(self, "_stratified", value)
+
+    @property
+    def grouped(self):
+        return getattr(self, "_grouped", False)
+
+    @grouped.setter
+    def grouped(self, value):
+        object.__setattr__(self, "_grouped", value)

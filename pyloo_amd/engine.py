@@ -378,6 +378,142 @@ class Engine:
                                            p(loo_i), p(lppd_i), p(agg), C.byref(nrep)))
         return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": int(nrep.value)}
 
+    # ------------------------------------------------------------------ k-fold cross-validation
+    @staticmethod
+    def _kfold_host_matrix(a):
+        a = a.detach().numpy() if _is_torch_tensor(a) else np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError("expected 2-D (n_obs, n_draws) matrices")
+        return a if a.dtype in (np.float64, np.float32) else a.astype(np.float64)
+
+    def _kfold_upload(self, a, device, rows=None):
+        """A host matrix on the device in the layout it has in memory (observations fastest stays so), cut to ``rows`` first."""
+        import torch
+
+        if self._host_obs_fastest(a):
+            base = a.T if rows is None else a.T[:, rows]
+            return torch.from_numpy(np.ascontiguousarray(base)).to(device).T
+        return torch.from_numpy(np.ascontiguousarray(a if rows is None else a[rows])).to(device)
+
+    def kfold(self, ll_full, fold_log_liks, folds, scale_value=1.0, nan_flag=True):
+        """K-fold cross-validation from per-fold log-likelihoods (``pla_kfold_lme`` + ``pla_kfold_reduce``).
+
+        ``ll_full`` (N, S): the full fit.  ``fold_log_liks``: K matrices, matrix k (label k + 1) holding the held-out
+        log-likelihood under fold k's draws, compact ``(n_val_k, S_k)`` with the rows in ascending observation order or full
+        ``(N, S_k)`` (told apart by ``shape[0]``).  ``folds`` (N,): labels 1..K.  NumPy arrays or CUDA tensors of ONE float
+        dtype; CUDA tensors are read in place through their strides, NumPy matrices are uploaded (full-form ones cut to their
+        held-out rows first).  The task index is built with torch on the device: the observations in a stable sort by fold.
+        Host ``folds`` are checked (labels 1..K, the rows of a compact matrix = the size of its fold: ``ValueError``); ``folds``
+        given as a CUDA tensor are TRUSTED, so that nothing synchronises: labels outside 1..K are clamped and a compact matrix
+        of the wrong height is read with clamped rows -- memory-safe, but the caller vouches for them (the fronts of
+        ``pyloo_amd.loo_kfold`` check on the host first).
+
+        Returns ``dict(elpd_i, lpd_full_i, p_i, kfold_i, agg)``: CUDA tensors when ``ll_full`` is one (nothing synchronised),
+        ndarrays otherwise.  ``agg`` as documented at ``pla_kfold_reduce``; ``nan_flag``: NaN of the full fit counts as -1e10."""
+        plan = self._kfold_plan(ll_full, fold_log_liks, folds)
+        out, nrep = self._kfold_lme(plan, nan_flag)
+        return self._kfold_finish(plan, out, nrep, scale_value)
+
+    def _kfold_plan(self, ll_full, fold_log_liks, folds):
+        """The matrices on the device, the task index and the source table of one :meth:`kfold` call."""
+        import torch
+
+        mats = [ll_full] + list(fold_log_liks)
+        K = len(mats) - 1
+        if K < 1:
+            raise ValueError("need at least one fold matrix")
+        on_device = [_is_torch_tensor(m) and m.is_cuda for m in mats]
+        mats = [m if d else self._kfold_host_matrix(m) for m, d in zip(mats, on_device)]
+        if any(m.ndim != 2 for m in mats):
+            raise ValueError("expected 2-D (n_obs, n_draws) matrices")
+        kinds = {str(m.dtype).split(".")[-1] for m in mats}
+        if len(kinds) != 1 or not kinds <= {"float32", "float64"}:
+            raise TypeError(f"the full and the fold matrices must share one dtype, float64 or float32; got {sorted(kinds)}")
+        f32 = kinds == {"float32"}
+        N = int(mats[0].shape[0])
+        if N < 1 or any(int(m.shape[1]) < 1 for m in mats):
+            raise ValueError("empty matrix")
+        dev = next((m.device for m, d in zip(mats, on_device) if d), torch.device("cuda", self.device))
+        full_form = [int(m.shape[0]) == N for m in mats[1:]]
+        folds_dev = _is_torch_tensor(folds) and folds.is_cuda
+        fh = None
+        if not folds_dev or any(f and not d for f, d in zip(full_form, on_device[1:])):
+            fh = (folds.detach().cpu().numpy() if _is_torch_tensor(folds) else np.asarray(folds)).reshape(-1).astype(np.int64)
+            if fh.size != N:
+                raise ValueError(f"Length of folds ({fh.size}) must match observations ({N})")
+            if fh.min() < 1 or fh.max() > K:
+                raise ValueError("Fold indices must be the integers 1..K")
+            counts_h = np.bincount(fh - 1, minlength=K)
+            for k, m in enumerate(mats[1:]):
+                if not full_form[k] and int(m.shape[0]) != counts_h[k]:
+                    raise ValueError(f"fold {k + 1}: matrix has {int(m.shape[0])} rows, expected {counts_h[k]} (held-out) or {N} (full form)")
+        for k in range(K):  # host matrices go up, full-form ones as their held-out rows only
+            if not on_device[k + 1]:
+                rows = np.where(fh == k + 1)[0] if full_form[k] else None
+                mats[k + 1] = self._kfold_upload(mats[k + 1], dev, rows)
+                full_form[k] = False
+        if not on_device[0]:
+            mats[0] = self._kfold_upload(mats[0], dev)
+        f = folds.to(device=dev, dtype=torch.int64).reshape(-1) if folds_dev else torch.from_numpy(fh).to(dev)
+        if f.numel() != N:
+            raise ValueError(f"Length of folds ({f.numel()}) must match observations ({N})")
+        # ---- the task index: source 0 takes every observation, source k the observations of fold k in ascending order
+        ar = torch.arange(N, dtype=torch.int64, device=dev)
+        order = torch.argsort(f, stable=True)
+        lab = (f[order] - 1).clamp_(0, K - 1)
+        counts = torch.bincount(lab, minlength=K)[:K]
+        ends = torch.cumsum(counts, 0)
+        pos = ar - (ends - counts)[lab]
+        is_full = torch.tensor(full_form, dtype=torch.bool).to(dev)
+        task_row = torch.cat([ar, torch.where(is_full[lab], order, pos)])
+        task_out = torch.cat([ar, order + N])
+        offsets = torch.cat([torch.tensor([0, N], dtype=torch.int64).to(dev), ends + N])
+        # ---- the source table (host arrays; the library uploads it)
+        shp = lambda m, i: int(m.shape[i])  # noqa: E731
+        base = np.array([m.data_ptr() for m in mats], dtype=np.uint64)
+        n_rows = np.array([shp(m, 0) for m in mats], dtype=np.int64)
+        n_draws = np.array([shp(m, 1) for m in mats], dtype=np.int64)
+        for i, m in enumerate(mats):
+            if (shp(m, 1) > 1 and m.stride(1) <= 0) or (shp(m, 0) > 1 and m.stride(0) < 0):
+                mats[i] = m.contiguous()
+                base[i] = mats[i].data_ptr()
+        s_row = np.array([m.stride(0) if shp(m, 0) > 1 else 0 for m in mats], dtype=np.int64)
+        s_draw = np.array([m.stride(1) if shp(m, 1) > 1 else 1 for m in mats], dtype=np.int64)
+        return {"mats": mats, "N": N, "K": K, "f32": f32, "dev": dev, "host_out": not on_device[0], "offsets": offsets,
+                "task_row": task_row, "task_out": task_out, "table": (base, n_rows, n_draws, s_row, s_draw)}
+
+    def _kfold_lme(self, plan, nan_flag=True):
+        """The ragged pass (``pla_kfold_lme``): ``(out, n_replaced)``, ``out[:N]`` the full fit's values, ``out[N:]`` the held-out ones."""
+        import torch
+
+        N, dev = plan["N"], plan["dev"]
+        out = torch.empty(2 * N, dtype=torch.float64, device=dev)
+        nrep = torch.zeros(1, dtype=torch.int64, device=dev)
+        pn = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        pt = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self._lib.pla_kfold_lme(self._h, *(pn(a) for a in plan["table"]), plan["K"] + 1,
+                                      _capi.PLA_F32 if plan["f32"] else _capi.PLA_F64, 1 if nan_flag else 0, pt(plan["offsets"]),
+                                      pt(plan["task_row"]), pt(plan["task_out"]), 2 * N, PLA_DEVICE, self._stream(), pt(out), 2 * N,
+                                      pt(nrep)))
+        return out, nrep
+
+    def _kfold_finish(self, plan, out, nrep, scale_value):
+        """The finishing pass (``pla_kfold_reduce``) and the result dictionary of :meth:`kfold`."""
+        import torch
+
+        N, dev = plan["N"], plan["dev"]
+        pt = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        lpd_full_i, elpd_i = out[:N], out[N:]
+        p_i = torch.empty(N, dtype=torch.float64, device=dev)
+        kfold_i = torch.empty(N, dtype=torch.float64, device=dev)
+        agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev)
+        check(self._lib.pla_kfold_reduce(self._h, pt(elpd_i), pt(lpd_full_i), N, float(scale_value), pt(nrep), PLA_DEVICE,
+                                         self._stream(), pt(p_i), pt(kfold_i), pt(agg)))
+        res = {"elpd_i": elpd_i, "lpd_full_i": lpd_full_i, "p_i": p_i, "kfold_i": kfold_i, "agg": agg}
+        if not plan["host_out"]:
+            return res
+        return {k: v.cpu().numpy() for k, v in res.items()}
+
     # ------------------------------------------------------------------ weights pass
     def importance_weights(self, logw, tail_count=0, method="psis"):
         """(n_obs, n_draws) log ratios -> (lw, diag) (``pla_importance_weights``)."""
