@@ -296,6 +296,37 @@ int pla_kfold_reduce(pla_engine *eng, const double *elpd, const double *lpd_full
                      double *kfold_i, double *agg);
 
 /*
+ * pla_mm_moments / pla_mm_transform / pla_mm_ratios -- the batched arithmetic of moment matching (loo_moment_match.py:656-914,
+ * split_moment_match.py:132-252) for B observations at once.  f64, DEVICE pointers only, contiguous arrays, everything enqueued on
+ * the caller's stream; the model evaluations between the calls and the D x D factorisations are the caller's.  n_draws >= 2.
+ *
+ * pla_mm_moments   upars (B, S, D), lw (B, S) log weights -> stats (B, 4, D): the plain mean, the weighted mean sum exp(lw) x,
+ *                  np.var (ddof 0) and the raw weighted second moment (sum w x^2 - wmean^2) * S / (S - 1) of shift_and_scale(), kept
+ *                  in that one-pass form; with want_cov != 0 also cov (B, 2, D, D): np.cov(rowvar=False) and np.cov(aweights=w),
+ *                  centred on the plain mean and on the weighted average (two passes), divisors S - 1 and W - W2 / W.  Several
+ *                  workgroups per b over tiles of S, the per-tile partials added in tile order by a second launch, no
+ *                  floating-point atomics: the bits depend neither on the grid (pla_engine_set_compare_grid caps it) nor on B.
+ *                  D <= 64 with want_cov, D <= 1024 without (PLA_ERR_UNSUPPORTED beyond).
+ * pla_mm_transform out[b, s, :] = (((x[b, s, :] - m0[b]) * pre[b]) . map[b]^T) / post_div[b] + m1[b] for rows s in [row_lo, row_hi),
+ *                  out[b, s, :] = x[b, s, :] for the others.  pre, map (B, D, D) and post_div may be NULL; x is (S, D) at
+ *                  x + b * x_batch_stride (0: one matrix for every b).  Without a matrix every operation is rounded as written
+ *                  (NumPy's bits).  D <= 64 with a matrix.  Not in place.
+ * pla_mm_ratios    mode 0: a = ll_new, b = lp_new (B, S), c = lp_orig (S) -> out (2B, S): rows [0, B) -ll + lp - lp_orig, rows
+ *                  [B, 2B) lp - lp_orig, NaN -> -inf.  mode 1: a = ll_half, b = lp_half, c = lp_half_inv (B, S), jac (B, 2) = (sum
+ *                  log total_scaling, log |det total_mapping|) -> out (B, S): the multiple-importance-sampling log weights of the
+ *                  split step, log1p(exp(.)) on the stable side, NaN / +inf -> -inf.  mode 2: out = a + b, NaN / +inf -> -inf.
+ *                  mode 3: a = ll, b = lw (B, S) -> out (B, 2): logsumexp(ll + lw) and logsumexp(ll) - log S, one wave per row.
+ */
+int pla_mm_moments(pla_engine *eng, const double *upars, const double *lw, int64_t n_batch, int64_t n_draws,
+                   int64_t n_dim, int want_cov, void *stream, double *stats, double *cov /* NULL without want_cov */);
+int pla_mm_transform(pla_engine *eng, const double *x, int64_t x_batch_stride, const double *m0,
+                     const double *pre /* may be NULL */, const double *map /* may be NULL */,
+                     const double *post_div /* may be NULL */, const double *m1, int64_t n_batch, int64_t n_draws,
+                     int64_t n_dim, int64_t row_lo, int64_t row_hi, void *stream, double *out);
+int pla_mm_ratios(pla_engine *eng, int mode, const double *a, const double *b, const double *c, const double *jac,
+                  int64_t n_batch, int64_t n_draws, void *stream, double *out);
+
+/*
  * pla_e_loo -- PSIS-weighted expectations of a same-shape matrix and their function-specific Pareto k.
  * Replaces, per observation, e_loo.py:214-236: `_normalize_log_weights` + `_compute_weighted_mean` (430-437, 557-559),
  * `_compute_weighted_variance` / `_wvar_func` (440-459, 518-531; sd = sqrt(variance), 462-465) and `compute_pareto_k` ->

@@ -17,6 +17,7 @@ PLA_MVN_NORMAL, PLA_MVN_STUDENT_T = 0, 1
 PLA_NONFACTOR_MAX_OBS = 1024
 # status word of a draw of pla_nonfactor_loglik
 NF_GENERAL, NF_SINGULAR, NF_NONFINITE, NF_DF_NONPOS, NF_BETA_NONFINITE, NF_CLAMPED = 1, 2, 4, 8, 16, 32
+PLA_MM_MAX_COV_DIM, PLA_MM_MAX_DIM = 64, 1024  # pla_mm_moments / pla_mm_transform: D with and without matrices
 NF_ROUTE_AUTO, NF_ROUTE_LDS, NF_ROUTE_WORKSPACE, NF_ROUTE_GENERAL = 0, 1, 2, 3
 
 # every symbol declared in include/pyloo_amd.h
@@ -31,6 +32,7 @@ SYMBOLS = (
     "pla_nonfactor_loglik", "pla_engine_set_nonfactor_route", "pla_engine_set_nonfactor_grid", "pla_nonfactor_lds_max_obs",
     "pla_gather_draws", "pla_psis_loo_draws", "pla_gather_lds_max_draws",
     "pla_kfold_lme", "pla_kfold_reduce",
+    "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
 )
 
 
@@ -109,6 +111,9 @@ def load_library():
     lib.pla_gather_lds_max_draws.argtypes = [ci]
     lib.pla_kfold_lme.argtypes = [vp, vp, vp, vp, vp, vp, i64, ci, ci, vp, vp, vp, i64, ci, vp, vp, i64, vp]
     lib.pla_kfold_reduce.argtypes = [vp, vp, vp, i64, dbl, vp, ci, vp, vp, vp, vp]
+    lib.pla_mm_moments.argtypes = [vp, vp, vp, i64, i64, i64, ci, vp, vp, vp]
+    lib.pla_mm_transform.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp]
+    lib.pla_mm_ratios.argtypes = [vp, ci, vp, vp, vp, vp, i64, i64, vp, vp]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

@@ -99,6 +99,8 @@ struct pla_engine {
   size_t h_kf_bytes[2] = {0, 0};
   hipEvent_t kf_event[2] = {nullptr, nullptr};
   int kf_turn = 0;
+  void* d_mm = nullptr;  // moment matching: per-tile partials of pla_mm_moments (pla_mm.h)
+  size_t d_mm_bytes = 0;
   std::string kf_label;  // the routes of the last pla_kfold_lme, for the text pla_kfold_reduce leaves in last_kernels
   int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
   int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
@@ -365,6 +367,7 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_nf_in) (void)hipFree(e->d_nf_in);
   if (e->d_nf_out) (void)hipFree(e->d_nf_out);
   if (e->d_kf) (void)hipFree(e->d_kf);
+  if (e->d_mm) (void)hipFree(e->d_mm);
   for (int i = 0; i < 2; ++i) {
     if (e->h_kf[i]) (void)hipHostFree(e->h_kf[i]);
     if (e->kf_event[i]) (void)hipEventDestroy(e->kf_event[i]);
@@ -1444,6 +1447,82 @@ int pla_kfold_reduce(pla_engine* eng, const double* elpd, const double* lpd_full
   const std::string finish = "kfold_tiles_kernel<0> + kfold_tiles_kernel<1> + kfold_final_kernel";
   eng->last_kernels = eng->kf_label.empty() ? finish : eng->kf_label + ", then " + finish;
   eng->kf_label.clear();
+  return PLA_OK;
+}
+
+// ---- moment matching (loo_moment_match.py:656-914, split_moment_match.py:132-252) -----------------------------------------------
+static int mm_check(pla_engine* eng, int64_t n_batch, int64_t n_draws, int64_t n_dim, bool matrices) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (n_batch < 0 || n_batch > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_batch out of range");
+  if (n_draws < 2 || n_draws > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_draws must lie in [2, 2^30], got %lld", (long long)n_draws);
+  if (n_dim < 1) return fail(PLA_ERR_ARG, "n_dim < 1");
+  if (matrices && n_dim > pla::kMmMaxCovDim)
+    return fail(PLA_ERR_UNSUPPORTED, "moment matching with covariance matrices takes at most %d parameters, got %lld", pla::kMmMaxCovDim,
+                (long long)n_dim);
+  if (n_dim > pla::kMmMaxDim)
+    return fail(PLA_ERR_UNSUPPORTED, "moment matching takes at most %d parameters, got %lld", pla::kMmMaxDim, (long long)n_dim);
+  return PLA_OK;
+}
+
+int pla_mm_moments(pla_engine* eng, const double* upars, const double* lw, int64_t n_batch, int64_t n_draws, int64_t n_dim, int want_cov,
+                   void* stream, double* stats, double* cov) {
+  int rc = mm_check(eng, n_batch, n_draws, n_dim, want_cov != 0);
+  if (rc) return rc;
+  if (n_batch > 0 && (!upars || !lw || !stats || (want_cov && !cov))) return fail(PLA_ERR_ARG, "upars, lw, stats or cov is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_batch == 0) return PLA_OK;
+  rc = grow(&eng->d_mm, &eng->d_mm_bytes, (size_t)pla::mm_moments_workspace(n_batch, n_draws, (int)n_dim, want_cov) * sizeof(double));
+  if (rc) return rc;
+  {
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_mm_moments(upars, lw, n_batch, n_draws, (int)n_dim, want_cov ? 1 : 0, (double*)eng->d_mm, stats, cov,
+                                   eng->compare_grid, s));
+  }
+  eng->last_kernels = std::string("mm_sums_kernel<0> + mm_mid_kernel + mm_sums_kernel<1> + ") + (want_cov ? "mm_cov_kernel + " : "") +
+                      "mm_fin_kernel";
+  return PLA_OK;
+}
+
+int pla_mm_transform(pla_engine* eng, const double* x, int64_t x_batch_stride, const double* m0, const double* pre, const double* map,
+                     const double* post_div, const double* m1, int64_t n_batch, int64_t n_draws, int64_t n_dim, int64_t row_lo,
+                     int64_t row_hi, void* stream, double* out) {
+  int rc = mm_check(eng, n_batch, n_draws, n_dim, map != nullptr);
+  if (rc) return rc;
+  if (n_batch > 0 && (!x || !m0 || !m1 || !out)) return fail(PLA_ERR_ARG, "x, m0, m1 or out is NULL");
+  if (x_batch_stride != 0 && x_batch_stride < n_draws * n_dim) return fail(PLA_ERR_ARG, "x_batch_stride must be 0 or at least n_draws * n_dim");
+  if (row_lo < 0 || row_hi > n_draws || row_lo > row_hi) return fail(PLA_ERR_ARG, "need 0 <= row_lo <= row_hi <= n_draws");
+  if (x == out) return fail(PLA_ERR_ARG, "the transform does not work in place");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_batch == 0) return PLA_OK;
+  pla::MmTransformParams p{x, x_batch_stride, m0, pre, map, post_div, m1, n_batch, n_draws, (int)n_dim, row_lo, row_hi, out};
+  {
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_mm_transform(p, eng->compare_grid, s));
+  }
+  eng->last_kernels = map ? "mm_map_kernel" : "mm_affine_kernel";
+  return PLA_OK;
+}
+
+int pla_mm_ratios(pla_engine* eng, int mode, const double* a, const double* b, const double* c, const double* jac, int64_t n_batch,
+                  int64_t n_draws, void* stream, double* out) {
+  int rc = mm_check(eng, n_batch, n_draws, 1, false);
+  if (rc) return rc;
+  if (mode < 0 || mode > 3) return fail(PLA_ERR_ARG, "mode must be 0 (update), 1 (split), 2 (sum) or 3 (finish)");
+  if (n_batch > 0 && (!a || !b || !out || (mode <= 1 && !c) || (mode == 1 && !jac))) return fail(PLA_ERR_ARG, "an input or out is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_batch == 0) return PLA_OK;
+  pla::MmRatiosParams p{a, b, c, jac, n_batch, n_draws, out};
+  {
+    TimedLaunch t(eng, s);
+    PLA_HIP(pla::launch_mm_ratios(mode, p, eng->compare_grid, s));
+  }
+  eng->last_kernels = mode == 3 ? "mm_finish_kernel" : "mm_ratios_kernel<" + std::to_string(mode) + ">";
   return PLA_OK;
 }
 

@@ -187,6 +187,38 @@ const char* kfold_route_name(int route);
 int64_t kfold_n_tiles(int64_t n_obs);
 hipError_t launch_kfold_reduce(const double* elpd, const double* lpd_full, int64_t n_obs, double scale, double* p_i, double* kfold_i,
                                double* part, const unsigned long long* replaced, double* agg, int grid_cap, hipStream_t stream);
+// moment matching (pla_mm.h): batched moments, affine transform and ratio assembly, f64, device memory
+constexpr int kMmMaxCovDim = 64;  // D with matrices (moments with cov, transform with a matrix)
+constexpr int kMmMaxDim = 1024;   // D without
+
+struct MmTransformParams {
+  const double* x;  // batch b at x + b * x_batch_stride (0: one matrix for every b), (S, D)
+  int64_t x_batch_stride;
+  const double* m0;    // [B][D]
+  const double* pre;   // [B][D] or null
+  const double* map;   // [B][D][D] or null
+  const double* post;  // [B][D] or null: a divisor
+  const double* m1;    // [B][D]
+  int64_t B, S;
+  int D;
+  int64_t row_lo, row_hi;
+  double* out;  // (B, S, D)
+};
+
+struct MmRatiosParams {
+  const double *a, *b, *c;  // see launch_mm_ratios
+  const double* jac;        // [B][2] (mode 1)
+  int64_t B, S;
+  double* out;
+};
+
+// work: mm_moments_workspace(...) doubles of engine workspace; grid_cap > 0 caps the workgroups of every launch (the results do
+// not depend on it).  mode of launch_mm_ratios: 0 update ratios, 1 split weights, 2 lw + ll, 3 the two logsumexp per row.
+int64_t mm_moments_workspace(int64_t B, int64_t S, int D, int want_cov);
+hipError_t launch_mm_moments(const double* x, const double* lw, int64_t B, int64_t S, int D, int want_cov, double* work, double* stats,
+                             double* cov, int grid_cap, hipStream_t stream);
+hipError_t launch_mm_transform(const MmTransformParams& p, int grid_cap, hipStream_t stream);
+hipError_t launch_mm_ratios(int mode, const MmRatiosParams& p, int grid_cap, hipStream_t stream);
 // largest tail count the kernels accept
 int max_tail_count();
 

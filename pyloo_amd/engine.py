@@ -514,6 +514,94 @@ class Engine:
             return res
         return {k: v.cpu().numpy() for k, v in res.items()}
 
+    # ------------------------------------------------------------------ moment matching
+    @staticmethod
+    def _mm_input(t, shape, what):
+        """A contiguous float64 CUDA tensor of the given shape (copied only when it is not one already)."""
+        import torch
+
+        if not _is_torch_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: expected a CUDA tensor")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.to(torch.float64).contiguous()
+
+    @staticmethod
+    def mm_check_dim(n_dim, matrices):
+        """The limits of the moment-matching kernels: ``ValueError`` beyond them."""
+        if matrices and n_dim > _capi.PLA_MM_MAX_COV_DIM:
+            raise ValueError(f"moment matching with cov=True takes at most {_capi.PLA_MM_MAX_COV_DIM} parameters, got {n_dim} "
+                             "(use cov=False)")
+        if n_dim > _capi.PLA_MM_MAX_DIM:
+            raise ValueError(f"moment matching takes at most {_capi.PLA_MM_MAX_DIM} parameters, got {n_dim}")
+
+    def mm_moments(self, upars, lw, cov=False):
+        """``upars`` (B, S, D), ``lw`` (B, S) log weights, CUDA f64 -> ``(stats, covs)`` (``pla_mm_moments``): ``stats`` (B, 4, D) =
+        plain mean, weighted mean ``sum exp(lw) x``, ``np.var`` and the raw weighted second moment of ``shift_and_scale``;
+        ``covs`` (B, 2, D, D) = ``np.cov(rowvar=False)`` and ``np.cov(aweights=exp(lw))``, or None without ``cov``.  Nothing is
+        synchronised; the bits depend neither on B nor on the grid."""
+        import torch
+
+        if not _is_torch_tensor(upars) or upars.dim() != 3:
+            raise ValueError("upars: expected a (B, S, D) CUDA tensor")
+        B, S, D = (int(v) for v in upars.shape)
+        self.mm_check_dim(D, cov)
+        x = self._mm_input(upars, (B, S, D), "upars")
+        w = self._mm_input(lw, (B, S), "lw")
+        stats = torch.empty((B, 4, D), dtype=torch.float64, device=x.device)
+        covs = torch.empty((B, 2, D, D), dtype=torch.float64, device=x.device) if cov else None
+        check(self._lib.pla_mm_moments(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), B, S, D, 1 if cov else 0,
+                                       self._stream(), C.c_void_p(stats.data_ptr()), C.c_void_p(covs.data_ptr()) if cov else None))
+        return stats, covs
+
+    def mm_transform(self, x, m0, m1, pre=None, mapping=None, post_div=None, rows=None):
+        """``out[b, s] = (((x[b, s] - m0[b]) * pre[b]) @ mapping[b].T) / post_div[b] + m1[b]`` for the rows ``s`` in ``rows = (lo, hi)``
+        (default: all), ``x[b, s]`` for the others (``pla_mm_transform``).  ``x`` is (B, S, D), or (S, D) shared by every b;
+        ``m0`` / ``m1`` / ``pre`` / ``post_div`` (B, D), ``mapping`` (B, D, D); CUDA f64.  Returns a new (B, S, D) tensor."""
+        import torch
+
+        if not _is_torch_tensor(m0) or m0.dim() != 2:
+            raise ValueError("m0: expected a (B, D) CUDA tensor")
+        B, D = (int(v) for v in m0.shape)
+        self.mm_check_dim(D, mapping is not None)
+        shared = x.dim() == 2
+        S = int(x.shape[-2])
+        x = self._mm_input(x, (S, D) if shared else (B, S, D), "x")
+        vec = lambda t, what: None if t is None else self._mm_input(t, (B, D), what)  # noqa: E731
+        m0, m1, pre, post_div = vec(m0, "m0"), vec(m1, "m1"), vec(pre, "pre"), vec(post_div, "post_div")
+        mapping = None if mapping is None else self._mm_input(mapping, (B, D, D), "mapping")
+        lo, hi = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
+        out = torch.empty((B, S, D), dtype=torch.float64, device=x.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self._lib.pla_mm_transform(self._h, p(x), 0 if shared else S * D, p(m0), p(pre), p(mapping), p(post_div), p(m1), B, S, D,
+                                         lo, hi, self._stream(), p(out)))
+        return out
+
+    def mm_ratios(self, mode, a, b, c=None, jac=None):
+        """The ratio assembly of moment matching (``pla_mm_ratios``), CUDA f64, ``a`` and ``b`` (B, S):
+        ``"update"``: a = ll_new, b = lp_new, c = lp_orig (S,) -> (2B, S), rows [0, B) ``-ll + lp - lp_orig``, rows [B, 2B)
+        ``lp - lp_orig``, NaN -> -inf; ``"split"``: a = ll_half, b = lp_half, c = lp_half_inv (B, S), jac (B, 2) -> (B, S);
+        ``"sum"``: ``a + b`` with NaN / +inf -> -inf; ``"finish"``: a = ll, b = lw -> (B, 2) = ``logsumexp(ll + lw)``,
+        ``logsumexp(ll) - log S``."""
+        import torch
+
+        code = {"update": 0, "split": 1, "sum": 2, "finish": 3}[mode]
+        if not _is_torch_tensor(a) or a.dim() != 2:
+            raise ValueError("a: expected a (B, S) CUDA tensor")
+        B, S = (int(v) for v in a.shape)
+        a, b = self._mm_input(a, (B, S), "a"), self._mm_input(b, (B, S), "b")
+        if code == 0:
+            c = self._mm_input(c, (S,), "c")
+        elif code == 1:
+            c, jac = self._mm_input(c, (B, S), "c"), self._mm_input(jac, (B, 2), "jac")
+        else:
+            c = jac = None
+        shape = {0: (2 * B, S), 1: (B, S), 2: (B, S), 3: (B, 2)}[code]
+        out = torch.empty(shape, dtype=torch.float64, device=a.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self._lib.pla_mm_ratios(self._h, code, p(a), p(b), p(c), p(jac), B, S, self._stream(), p(out)))
+        return out
+
     # ------------------------------------------------------------------ weights pass
     def importance_weights(self, logw, tail_count=0, method="psis"):
         """(n_obs, n_draws) log ratios -> (lw, diag) (``pla_importance_weights``)."""
