@@ -327,6 +327,55 @@ int pla_mm_ratios(pla_engine *eng, int mode, const double *a, const double *b, c
                   int64_t n_batch, int64_t n_draws, void *stream, double *out);
 
 /*
+ * pla_mixis_draw_lse / pla_mixis_loo -- Mix-IS-LOO (Silva & Zanella 2022; the estimator loo.py:252-284 and elpd.py:364-374
+ * document) in two passes over the (n_obs, n_draws) matrix, one log-sum-exp along each axis:
+ *     c[s]     = log sum_i exp(-ll[i, s])                                  pla_mixis_draw_lse: one value per DRAW
+ *     loo_i[i] = scale_value * (LSE_s(-c) - LSE_s(-ll[i, s] - c[s]))       pla_mixis_loo
+ * (The reference's code reduces the first sum over the draws, which makes every pointwise value the same constant; DESIGN.md
+ * section 10 has the finding and a 2 x 2 case.)  No Pareto fit, no refit.  All arithmetic is f64, f32 is widened on load.  On load
+ * NaN counts as -1e10, +inf as +1e10 and -inf as -1e10, in both passes alike; everything behind the load is plain IEEE.
+ *
+ *   ll, dtype, n_obs, n_draws, strides   as pla_psis_loo; 1 <= n_obs < 2^40, 1 <= n_draws <= 2^30.  PLA_DEVICE: any strides, read
+ *                in place.  PLA_HOST: unit stride along the draws or along the observations (other strides:
+ *                PLA_ERR_UNSUPPORTED); the matrix goes through the staging buffer in blocks of whole tiles of pass 1 (1 GiB, or
+ *                PLA_INGEST_BLOCK_MB), each in the matrix's own layout, ONCE PER PASS: pla_mixis_draw_lse followed by
+ *                pla_mixis_loo, or pla_mixis_loo without a c, move it to the device twice.  The staged kernels are those a compact
+ *                (pitch = line length), 16-byte aligned device matrix of that layout gets: such a device matrix and the host
+ *                matrix give the same bits, whatever the block size.  (A device matrix with a padded pitch or an unaligned base
+ *                may take the other vector width of the line / register-row kernels and differ in the last bits.)
+ *   c            [n_draws] double in the memory space of ll.  pla_mixis_draw_lse writes it; pla_mixis_loo reads it, or computes it
+ *                itself when it is NULL (one call, two passes).  It is an argument so that the front reports the replaced
+ *                entries once and a sharded caller can merge c across ranks between the passes.
+ *   n_replaced   [2] int64 in the memory space of ll (may be NULL): NaN entries, +-inf entries met by pass 1
+ *   loo_i        [n_obs] double (may be NULL)
+ *   agg          [PLA_AGG_COUNT] (may be NULL), the slots of pla_psis_loo reused: [PLA_AGG_N] n_obs, [PLA_AGG_SUM_LOO] sum loo_i,
+ *                [PLA_AGG_M2_LOO] sum (loo_i - mean)^2 (two-pass about the mean, as np.var: se = sqrt(M2)), [PLA_AGG_N_SLOW] the
+ *                entries pass 2 replaced on load (NaN and +-inf together, as pla_waic), the others 0
+ *   routes       pass 1 cuts the observations into tiles of pla_mixis_tile_rows(n_obs) rows -- max(256, ceil(n_obs / 128) rounded
+ *                up to 256), a rule of n_obs alone, so at most 128 tiles -- keeps one (maximum, rescaled sum) per tile and draw in
+ *                a slab of engine workspace (2 * tiles * n_draws doubles: at most 2048 * n_draws bytes) and merges a draw's
+ *                partials in tile order.  Unit draw stride: lanes own adjacent draws and walk down a tile's rows; unit
+ *                observation stride: a wavefront per (draw, tile) reads its piece of the draw's line with 16-byte loads (element
+ *                loads when the lines are not 16-byte aligned); other strides: the first kernel with both strides.  Pass 2, unit
+ *                draw stride: a wavefront per observation -- rows of at most 4096 draws in its registers with c staged in LDS
+ *                (exact maximum, then the sum), longer rows streamed with c read through L2; unit observation stride: a lane per
+ *                observation, c[s] wave-uniform in a scalar register (scalar loads); other strides: a workgroup per observation.  The scale and the aggregates are
+ *                the tile-ordered finishing pass of pla_kfold_reduce.  No floating-point atomics anywhere: the same input gives
+ *                the same bits whatever the grid (pla_engine_set_mixis_grid caps the workgroups of every launch; 0: the
+ *                library's choice).  pla_engine_last_kernels names the kernels taken.
+ * pla_mixis_tile_rows needs no engine and no GPU; it returns the tile height (> 0) or a negative status.
+ * Everything is enqueued on the caller's stream; PLA_HOST calls return when the results are in the caller's arrays.
+ */
+int pla_mixis_draw_lse(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                       int64_t stride_draw, int mem_space, void *stream, double *c,
+                       int64_t *n_replaced /* [2], may be NULL */);
+int pla_mixis_loo(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                  int64_t stride_draw, const double *c /* NULL: computed by the call */, double scale_value, int mem_space,
+                  void *stream, double *loo_i /* may be NULL */, double *agg /* may be NULL */);
+int pla_engine_set_mixis_grid(pla_engine *eng, int max_workgroups);
+int pla_mixis_tile_rows(int64_t n_obs);
+
+/*
  * pla_e_loo -- PSIS-weighted expectations of a same-shape matrix and their function-specific Pareto k.
  * Replaces, per observation, e_loo.py:214-236: `_normalize_log_weights` + `_compute_weighted_mean` (430-437, 557-559),
  * `_compute_weighted_variance` / `_wvar_func` (440-459, 518-531; sd = sqrt(variance), 462-465) and `compute_pareto_k` ->

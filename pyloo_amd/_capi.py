@@ -33,6 +33,7 @@ SYMBOLS = (
     "pla_gather_draws", "pla_psis_loo_draws", "pla_gather_lds_max_draws",
     "pla_kfold_lme", "pla_kfold_reduce",
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
+    "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
 )
 
 
@@ -114,6 +115,10 @@ def load_library():
     lib.pla_mm_moments.argtypes = [vp, vp, vp, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_mm_transform.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp]
     lib.pla_mm_ratios.argtypes = [vp, ci, vp, vp, vp, vp, i64, i64, vp, vp]
+    lib.pla_mixis_draw_lse.argtypes = [vp, vp, ci, i64, i64, i64, i64, ci, vp, vp, vp]
+    lib.pla_mixis_loo.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, dbl, ci, vp, vp, vp]
+    lib.pla_engine_set_mixis_grid.argtypes = [vp, ci]
+    lib.pla_mixis_tile_rows.argtypes = [i64]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -101,6 +102,9 @@ struct pla_engine {
   int kf_turn = 0;
   void* d_mm = nullptr;  // moment matching: per-tile partials of pla_mm_moments (pla_mm.h)
   size_t d_mm_bytes = 0;
+  void* d_mix = nullptr;  // Mix-IS-LOO (pla_mixis.h): the slab of pass 1, c, the unscaled pointwise values, the finishing pass's partials
+  size_t d_mix_bytes = 0;
+  int mixis_grid = 0;  // pla_engine_set_mixis_grid (0: the library's choice)
   std::string kf_label;  // the routes of the last pla_kfold_lme, for the text pla_kfold_reduce leaves in last_kernels
   int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
   int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
@@ -368,6 +372,7 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_nf_out) (void)hipFree(e->d_nf_out);
   if (e->d_kf) (void)hipFree(e->d_kf);
   if (e->d_mm) (void)hipFree(e->d_mm);
+  if (e->d_mix) (void)hipFree(e->d_mix);
   for (int i = 0; i < 2; ++i) {
     if (e->h_kf[i]) (void)hipHostFree(e->h_kf[i]);
     if (e->kf_event[i]) (void)hipEventDestroy(e->kf_event[i]);
@@ -1447,6 +1452,194 @@ int pla_kfold_reduce(pla_engine* eng, const double* elpd, const double* lpd_full
   const std::string finish = "kfold_tiles_kernel<0> + kfold_tiles_kernel<1> + kfold_final_kernel";
   eng->last_kernels = eng->kf_label.empty() ? finish : eng->kf_label + ", then " + finish;
   eng->kf_label.clear();
+  return PLA_OK;
+}
+
+// ---- Mix-IS-LOO (pla_mixis.h) -----------------------------------------------------------------------------------------------------
+static int mixis_check(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                       int64_t stride_draw, int mem_space) {
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (n_obs < 1 || n_obs >= ((int64_t)1 << 40)) return fail(PLA_ERR_ARG, "n_obs must lie in [1, 2^40), got %lld", (long long)n_obs);
+  if (n_draws < 1 || n_draws > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_draws must lie in [1, 2^30], got %lld", (long long)n_draws);
+  if (!ll) return fail(PLA_ERR_ARG, "the matrix pointer is NULL");
+  if (stride_obs < 0 || stride_draw < 0 || (n_obs > 1 && stride_obs == 0) || (n_draws > 1 && stride_draw == 0))
+    return fail(PLA_ERR_ARG, "bad strides");
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (mem_space == PLA_HOST && !(stride_draw == 1 && (n_obs == 1 || stride_obs >= n_draws)) &&
+      !(stride_obs == 1 && (n_draws == 1 || stride_draw >= n_obs)))
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST input needs unit stride along the draws or along the observations");
+  return PLA_OK;
+}
+
+// the sections of pla_engine::d_mix, in doubles
+struct MixisWorkspace {
+  size_t slab, c, lse, elpd, loo, agg, part, counts, total;
+  MixisWorkspace(int64_t n_obs, int64_t n_draws) {
+    const auto even = [](size_t n) { return (n + 1) & ~(size_t)1; };
+    slab = 0;
+    c = slab + 2 * (size_t)pla::mixis_n_tiles(n_obs) * (size_t)n_draws;
+    lse = c + even((size_t)n_draws);
+    elpd = lse + 2;
+    loo = elpd + even((size_t)n_obs);  // (the scaled values of a PLA_HOST call)
+    agg = loo + even((size_t)n_obs);
+    part = agg + PLA_AGG_COUNT;
+    counts = part + 4 * (size_t)pla::kfold_n_tiles(n_obs);
+    total = counts + 2;
+  }
+};
+
+// A PLA_HOST matrix goes through the staging buffer in blocks of whole tiles of pass 1, once per pass, each block in the matrix's own
+// layout: rows [r0, r0 + nr) as an (nr, n_draws) block (draws fastest) or as an (n_draws, nr) slab whose pitch is nr rounded up to
+// 16 bytes (observations fastest).  Block size: 1 GiB, or PLA_INGEST_BLOCK_MB (read per call).  f(ptr, r0, nr, stride_obs,
+// stride_draw, vec_pitch) runs the kernels on one block; a device matrix is one block, read in place.
+static int64_t mixis_block_rows(int64_t n_obs, int64_t n_draws, size_t esz) {
+  const char* e = getenv("PLA_INGEST_BLOCK_MB");
+  const long mb = e ? atol(e) : 0;
+  const size_t bytes = mb > 0 ? (size_t)mb << 20 : (size_t)1 << 30;
+  const int64_t t = pla::mixis_tile_rows_for(n_obs);
+  int64_t r = (int64_t)(bytes / ((size_t)n_draws * esz)) / t * t;
+  if (r < t) r = t;
+  return r < n_obs ? r : n_obs;
+}
+
+using MixisBlockFn = std::function<int(const void*, int64_t, int64_t, int64_t, int64_t, int64_t)>;
+static int mixis_blocks(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                        int64_t stride_draw, int mem_space, hipStream_t s, const MixisBlockFn& f) {
+  if (mem_space == PLA_DEVICE) return f(ll, (int64_t)0, n_obs, stride_obs, stride_draw, stride_draw);
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const bool draws_fastest = stride_draw == 1 && (n_obs == 1 || stride_obs >= n_draws);
+  const int64_t rows = mixis_block_rows(n_obs, n_draws, esz);
+  const int64_t pitch = draws_fastest ? n_draws : (rows + 3) / 4 * 4;  // of the staged block, elements
+  int rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)(draws_fastest ? rows : n_draws) * (size_t)pitch * esz);
+  if (rc) return rc;
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+    const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+    if (draws_fastest) {
+      PLA_HIP(hipMemcpy2DAsync(eng->d_in, (size_t)n_draws * esz, (const char*)ll + (size_t)r0 * (size_t)stride_obs * esz,
+                               (size_t)(n_obs == 1 ? n_draws : stride_obs) * esz, (size_t)n_draws * esz, (size_t)nr,
+                               hipMemcpyHostToDevice, s));
+      rc = f(eng->d_in, r0, nr, n_draws, (int64_t)1, (int64_t)1);
+    } else {
+      PLA_HIP(hipMemcpy2DAsync(eng->d_in, (size_t)pitch * esz, (const char*)ll + (size_t)r0 * esz,
+                               (size_t)(n_draws == 1 ? n_obs : stride_draw) * esz, (size_t)nr * esz, (size_t)n_draws,
+                               hipMemcpyHostToDevice, s));
+      rc = f(eng->d_in, r0, nr, (int64_t)1, pitch, n_obs);  // (16-byte loads where a device matrix of pitch n_obs takes them)
+    }
+    if (rc) return rc;
+    PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next block
+  }
+  return PLA_OK;
+}
+
+static int mixis_pass1(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                       int64_t stride_draw, int mem_space, hipStream_t s, double* slab, double* c, unsigned long long* replaced,
+                       char* route, int cap) {
+  int rc = mixis_blocks(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, mem_space, s,
+                        [&](const void* p, int64_t r0, int64_t nr, int64_t so, int64_t sd, int64_t vec_pitch) -> int {
+                          PLA_HIP(pla::launch_mixis_c(p, dtype, nr, (int)n_draws, so, sd, n_obs, r0, vec_pitch, slab, replaced,
+                                                      eng->mixis_grid, s, route, cap));
+                          return PLA_OK;
+                        });
+  if (rc) return rc;
+  PLA_HIP(pla::launch_mixis_c_merge(slab, n_obs, (int)n_draws, c, eng->mixis_grid, s));
+  return PLA_OK;
+}
+
+int pla_mixis_tile_rows(int64_t n_obs) {
+  if (n_obs < 1 || n_obs >= ((int64_t)1 << 40)) return fail(PLA_ERR_ARG, "n_obs must lie in [1, 2^40), got %lld", (long long)n_obs);
+  return (int)pla::mixis_tile_rows_for(n_obs);
+}
+
+int pla_engine_set_mixis_grid(pla_engine* eng, int max_workgroups) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (max_workgroups < 0) return fail(PLA_ERR_ARG, "max_workgroups < 0");
+  EngineCall call(eng);
+  eng->mixis_grid = max_workgroups;
+  return PLA_OK;
+}
+
+static const char* mixis_where(bool host) { return host ? "(matrix staged in blocks)" : "(matrix read in place)"; }
+
+int pla_mixis_draw_lse(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs,
+                       int64_t stride_draw, int mem_space, void* stream, double* c, int64_t* n_replaced) {
+  int rc = mixis_check(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, mem_space);
+  if (rc) return rc;
+  if (!c) return fail(PLA_ERR_ARG, "c is NULL");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const MixisWorkspace w(n_obs, n_draws);
+  rc = grow(&eng->d_mix, &eng->d_mix_bytes, w.total * sizeof(double));
+  if (rc) return rc;
+  double* ws = (double*)eng->d_mix;
+  const bool host = mem_space == PLA_HOST;
+  PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));  // [1] NaN, [2] +-inf
+  char route[96];
+  double* dc = host ? ws + w.c : c;
+  int64_t* dcounts = (int64_t*)(ws + w.counts);
+  {
+    TimedLaunch t(eng, s);
+    rc = mixis_pass1(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, mem_space, s, ws + w.slab, dc, eng->counters + 1, route,
+                     (int)sizeof(route));
+    if (rc) return rc;
+  }
+  if (n_replaced) PLA_HIP(pla::launch_mixis_counts(eng->counters + 1, nullptr, host ? dcounts : n_replaced, s));
+  eng->last_kernels = std::string(route) + " + mixis_c_merge_kernel " + mixis_where(host);
+  if (host) {
+    PLA_HIP(hipMemcpyAsync(c, dc, (size_t)n_draws * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (n_replaced) PLA_HIP(hipMemcpyAsync(n_replaced, dcounts, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    PLA_HIP(hipStreamSynchronize(s));
+  }
+  return PLA_OK;
+}
+
+int pla_mixis_loo(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                  const double* c, double scale_value, int mem_space, void* stream, double* loo_i, double* agg) {
+  int rc = mixis_check(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, mem_space);
+  if (rc) return rc;
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const MixisWorkspace w(n_obs, n_draws);
+  rc = grow(&eng->d_mix, &eng->d_mix_bytes, w.total * sizeof(double));
+  if (rc) return rc;
+  double* ws = (double*)eng->d_mix;
+  const bool host = mem_space == PLA_HOST;
+  char route1[96] = "", route2[96];
+  const double* dc = c;
+  TimedLaunch t(eng, s);
+  if (!c) {  // pass 1 by this call (its count of replaced entries is pass 2's)
+    rc = mixis_pass1(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, mem_space, s, ws + w.slab, ws + w.c, nullptr, route1,
+                     (int)sizeof(route1));
+    if (rc) return rc;
+    dc = ws + w.c;
+  } else if (host) {
+    PLA_HIP(hipMemcpyAsync(ws + w.c, c, (size_t)n_draws * sizeof(double), hipMemcpyHostToDevice, s));
+    dc = ws + w.c;
+  }
+  PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));  // [1] NaN, [2] +-inf
+  PLA_HIP(pla::launch_mixis_lse_c(dc, (int)n_draws, ws + w.lse, s));
+  rc = mixis_blocks(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, mem_space, s,
+                    [&](const void* p, int64_t r0, int64_t nr, int64_t so, int64_t sd, int64_t) -> int {
+                      PLA_HIP(pla::launch_mixis_elpd(p, dtype, nr, (int)n_draws, so, sd, dc, ws + w.lse, ws + w.elpd + r0,
+                                                     eng->counters + 1, eng->mixis_grid, s, route2, (int)sizeof(route2)));
+                      return PLA_OK;
+                    });
+  if (rc) return rc;
+  // the scale and the aggregates: the k-fold finishing pass on (elpd, elpd) -- kfold_i = scale * elpd, p_i = 0
+  double* dloo = host ? (loo_i ? ws + w.loo : nullptr) : loo_i;
+  double* dagg = host || !agg ? ws + w.agg : agg;
+  PLA_HIP(pla::launch_kfold_reduce(ws + w.elpd, ws + w.elpd, n_obs, scale_value, nullptr, dloo, ws + w.part, nullptr, dagg,
+                                   eng->mixis_grid, s));
+  PLA_HIP(pla::launch_mixis_counts(eng->counters + 1, dagg, nullptr, s));
+  eng->last_kernels = (route1[0] ? std::string(route1) + " + mixis_c_merge_kernel, then " : std::string()) + "mixis_lse_c_kernel + " +
+                      route2 + ", then kfold_tiles_kernel<0> + kfold_tiles_kernel<1> + kfold_final_kernel " + mixis_where(host);
+  if (host) {
+    if (loo_i) PLA_HIP(hipMemcpyAsync(loo_i, dloo, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (agg) PLA_HIP(hipMemcpyAsync(agg, dagg, PLA_AGG_COUNT * sizeof(double), hipMemcpyDeviceToHost, s));
+    PLA_HIP(hipStreamSynchronize(s));
+  }
   return PLA_OK;
 }
 

@@ -187,6 +187,27 @@ const char* kfold_route_name(int route);
 int64_t kfold_n_tiles(int64_t n_obs);
 hipError_t launch_kfold_reduce(const double* elpd, const double* lpd_full, int64_t n_obs, double scale, double* p_i, double* kfold_i,
                                double* part, const unsigned long long* replaced, double* agg, int grid_cap, hipStream_t stream);
+// Mix-IS-LOO (pla_mixis.h).  Pass 1: c[n_draws] = log sum_i exp(-ll[i, s]).  launch_mixis_c reduces rows [row0, row0 + n_rows) of a
+// matrix of n_obs rows (`in` points at row row0; row0 a multiple of mixis_tile_rows_for(n_obs): a host matrix comes in blocks of
+// whole tiles) into the tiles' slots of part -- 2 * mixis_n_tiles(n_obs) * n_draws doubles of engine workspace -- and
+// launch_mixis_c_merge combines the slots of every draw in tile order.  vec_pitch: the pitch that decides whether the line kernel
+// takes 16-byte loads beside the alignment of `in` and stride_draw (a staged block passes the whole matrix's, so that it sums in
+// the order a device matrix of that layout gets).  Pass 2: *lse_c = log sum_s exp(-c[s]) (launch_mixis_lse_c, once) and
+// elpd[i] = *lse_c - log sum_s exp(-ll[i, s] - c[s]), unscaled, for the rows at `in`.
+// replaced [2]: NaN and +-inf entries met (may be null); grid_cap > 0 caps the workgroups of every launch (the results do not
+// depend on it); route: text for pla_engine_last_kernels.
+int64_t mixis_tile_rows_for(int64_t n_obs);
+int64_t mixis_n_tiles(int64_t n_obs);
+hipError_t launch_mixis_c(const void* in, int dtype, int64_t n_rows, int n_draws, int64_t stride_obs, int64_t stride_draw,
+                          int64_t n_obs, int64_t row0, int64_t vec_pitch, double* part, unsigned long long* replaced, int grid_cap,
+                          hipStream_t stream, char* route, int cap);
+hipError_t launch_mixis_c_merge(const double* part, int64_t n_obs, int n_draws, double* c, int grid_cap, hipStream_t stream);
+hipError_t launch_mixis_lse_c(const double* c, int n_draws, double* lse_c, hipStream_t stream);
+hipError_t launch_mixis_elpd(const void* in, int dtype, int64_t n_obs, int n_draws, int64_t stride_obs, int64_t stride_draw,
+                             const double* c, const double* lse_c, double* elpd, unsigned long long* replaced, int grid_cap,
+                             hipStream_t stream, char* route, int cap);
+// agg[PLA_AGG_N_SLOW] = replaced[0] + replaced[1], agg[PLA_AGG_N_NONFINITE] = 0 (agg may be null); counts[2] = replaced (may be null)
+hipError_t launch_mixis_counts(const unsigned long long* replaced, double* agg, int64_t* counts, hipStream_t stream);
 // moment matching (pla_mm.h): batched moments, affine transform and ratio assembly, f64, device memory
 constexpr int kMmMaxCovDim = 64;  // D with matrices (moments with cov, transform with a matrix)
 constexpr int kMmMaxDim = 1024;   // D without

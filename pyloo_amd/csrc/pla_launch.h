@@ -1,6 +1,6 @@
 // Host-side pieces shared by the translation units of libpyloo_amd.so (internal).  The kernels are compiled as several
 // units in parallel (pyloo_amd/build.py): pla_k_general.hip (general kernel, reductions, dispatcher), pla_k_wave_f64/f32.hip,
-// pla_k_chunked_f64/f32.hip, pla_k_fit.hip, pla_k_waic.hip, pla_k_col.hip, pla_k_eloo.hip, pla_k_group.hip, pla_k_compare.hip, pla_k_nonfactor.hip, pla_k_draws.hip, pla_k_kfold.hip, pla_k_mm.hip; each launches the kernels it defines.
+// pla_k_chunked_f64/f32.hip, pla_k_fit.hip, pla_k_waic.hip, pla_k_col.hip, pla_k_eloo.hip, pla_k_group.hip, pla_k_compare.hip, pla_k_nonfactor.hip, pla_k_draws.hip, pla_k_kfold.hip, pla_k_mm.hip, pla_k_mixis.hip; each launches the kernels it defines.
 #pragma once
 
 #include <cstdlib>
@@ -19,7 +19,7 @@ namespace pla {
 //                            plain fit kernel (a test sets 1)
 //   PLA_FORCE_PATH=1         general kernel only
 //   PLA_INGEST_TRANSPOSE=1   observations-fastest device matrices through the transposing ingestion instead of being read in place
-//   PLA_INGEST_BLOCK_MB      block size of that ingestion (and of the group-sum buffer of pla_psis_loo_groups)
+//   PLA_INGEST_BLOCK_MB      block size of that ingestion (and of the group-sum buffer of pla_psis_loo_groups, and of the host staging of the Mix-IS passes)
 // pla_env_overrides() (C ABI) names the ones that are set, so that a benchmark record can say which arrangement ran.
 // Everything else -- phase ablation, grids, priorities, switching checks off: knobs that change timings or even results -- exists
 // only in builds with -DPLA_EXPERIMENT (tools/build_alt.sh) and is compiled out of the default library.

@@ -2,7 +2,8 @@
 
 Mirrors the LOO part of the reference container (pyloo/elpd.py:100-498): same index keys,
 same properties, same printed report (README.md:76-84 of the reference; the LOGO report of elpd.py:165-220), including the Pareto-k
-table with bins ``(-inf, good_k], (good_k, 1], (1, inf)`` (elpd.py:300-330), and the k-fold report (elpd.py:64-72, 130-163).  The
+table with bins ``(-inf, good_k], (good_k, 1], (1, inf)`` (elpd.py:300-330), the k-fold report (elpd.py:64-72, 130-163) and the
+report of a Mix-IS-LOO result, which has no ``p_loo`` (elpd.py:364-374).  The
 sub-sampling and non-factorised report variants are out of scope.
 """
 
@@ -19,6 +20,13 @@ Computed from {n_samples} posterior samples and {n_points} observations log-like
 elpd_loo   {elpd:<8.2f}    {se:<.2f}
 p_loo       {p_loo:<8.2f}    {p_loo_se:<.2f}
 looic      {looic:<8.2f}    {looic_se:<.2f}"""
+
+_MIXTURE_REPORT = """
+Computed from {n_samples} posterior samples and {n_points} observations log-likelihood matrix with
+mixture posterior.
+
+         Estimate       SE
+elpd_loo   {elpd:<8.2f}    -"""
 
 _WAIC_REPORT = """
 Computed from {n_samples} posterior samples and {n_points} observations log-likelihood matrix.
@@ -63,6 +71,14 @@ _SOME_HIGH = (
 _WARNED = "\n\nThere has been a warning during the calculation. Please check the results."
 
 
+def _k_values(k):
+    """The Pareto k of a result as a flat float array: a DataArray, an ndarray or a device tensor (``loo_i`` and ``pareto_k`` of a
+    ``*_from_matrix`` call on a CUDA tensor stay on the device)."""
+    if hasattr(k, "detach"):
+        k = k.detach().cpu().numpy()
+    return np.asarray(getattr(k, "values", k), dtype=float).ravel()
+
+
 class ELPDData(pd.Series):
     """Expected-log-pointwise-predictive-density results with a friendly ``print``."""
 
@@ -94,7 +110,7 @@ class ELPDData(pd.Series):
         tail = ""
         if "pareto_k" in self and self.get("good_k", None) is not None:
             gk = self["good_k"]
-            kv = np.asarray(getattr(self["pareto_k"], "values", self["pareto_k"]), dtype=float).ravel()
+            kv = _k_values(self["pareto_k"])
             counts = np.histogram(kv, bins=np.asarray([-np.inf, gk, 1, np.inf]))[0]
             if counts[1] == 0 and counts[2] == 0:
                 tail = _ALL_GOOD.format(gk=gk)
@@ -104,10 +120,13 @@ class ELPDData(pd.Series):
                                        p0=pct[0], p1=pct[1], p2=pct[2])
         elif self.method == "psis":
             tail = (_SOME_HIGH if self.warning else _ALL_GOOD).format(gk=0.7)
-        text = _REPORT.format(
-            n_samples=self.n_samples, n_points=self.n_data_points, elpd=self["elpd_loo"], se=self["se"],
-            p_loo=self["p_loo"], p_loo_se=self["p_loo_se"], looic=self["looic"], looic_se=self["looic_se"],
-        )
+        if "p_loo" not in self and "looic" not in self and "se" in self:  # a Mix-IS-LOO result (elpd.py:364-374): its index, whole
+            text = _MIXTURE_REPORT.format(n_samples=self.n_samples, n_points=self.n_data_points, elpd=self["elpd_loo"])
+        else:
+            text = _REPORT.format(
+                n_samples=self.n_samples, n_points=self.n_data_points, elpd=self["elpd_loo"], se=self["se"],
+                p_loo=self["p_loo"], p_loo_se=self["p_loo_se"], looic=self["looic"], looic_se=self["looic_se"],
+            )
         if self.warning:
             text += _WARNED
         return text + tail
@@ -121,7 +140,7 @@ class ELPDData(pd.Series):
             text += _WARNED
         if "pareto_k" in self and self.get("good_k", None) is not None:
             gk = self["good_k"]
-            kv = np.asarray(getattr(self["pareto_k"], "values", self["pareto_k"]), dtype=float).ravel()
+            kv = _k_values(self["pareto_k"])
             counts = np.histogram(kv, bins=np.asarray([-np.inf, gk, 1, np.inf]))[0]
             if counts[1] == 0 and counts[2] == 0:
                 text += _ALL_GOOD.format(gk=gk)

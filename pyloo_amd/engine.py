@@ -674,6 +674,80 @@ class Engine:
                                  float(scale_value), PLA_HOST, None, p(lppd_i), p(var_i), p(waic_i), p(agg)))
         return {"lppd_i": lppd_i, "var_i": var_i, "waic_i": waic_i, "agg": agg}
 
+    # ------------------------------------------------------------------ Mix-IS-LOO passes
+    def _mixis_input(self, ll):
+        """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None): a CUDA tensor is read in place
+        whatever its strides, a host array in either of the two layouts the library uploads."""
+        if _is_torch_tensor(ll):
+            import torch
+
+            if ll.dim() != 2 or not ll.is_cuda:
+                raise ValueError("expected a 2-D CUDA tensor")
+            if ll.dtype not in (torch.float64, torch.float32):
+                raise TypeError(f"unsupported dtype {ll.dtype}")
+            code = _capi.PLA_F64 if ll.dtype == torch.float64 else _capi.PLA_F32
+            return ll, ll.shape[0], ll.shape[1], ll.stride(0), ll.stride(1), code, PLA_DEVICE, self._stream(), ll.device
+        a = self._as_2d_host(ll, allow_obs_fastest=True)
+        so, sd = self._host_strides(a)
+        return a, a.shape[0], a.shape[1], so, sd, dtype_code(a.dtype), PLA_HOST, None, None
+
+    @staticmethod
+    def _mixis_ptr(x):
+        if x is None:
+            return None
+        return C.c_void_p(x.data_ptr()) if _is_torch_tensor(x) else x.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def _mixis_new(n, device, dtype="float64"):
+        if device is None:
+            return np.zeros(n, dtype=dtype)
+        import torch
+
+        return torch.zeros(n, dtype=getattr(torch, dtype), device=device)
+
+    def mixis_draw_lse(self, ll):
+        """Pass 1 of Mix-IS-LOO (``pla_mixis_draw_lse``): (n_obs, n_draws) log-likelihood -> ``dict(c, n_replaced)`` with
+        ``c[s] = log sum_i exp(-ll[i, s])`` and the counts of NaN and of infinite entries met, where the matrix lives."""
+        a, n, s, so, sd, code, space, stream, device = self._mixis_input(ll)
+        c = self._mixis_new(s, device)
+        nrep = self._mixis_new(2, device, "int64")
+        p = self._mixis_ptr
+        check(self._lib.pla_mixis_draw_lse(self._h, p(a), code, n, s, so, sd, space, stream, p(c), p(nrep)))
+        return {"c": c, "n_replaced": nrep}
+
+    def mixis_loo(self, ll, c=None, scale_value=1.0, pointwise=True, aggregate=True):
+        """Mix-IS-LOO (``pla_mixis_loo``): ``dict(loo_i, c, agg)`` with ``loo_i = scale * (LSE_s(-c) - LSE_s(-ll[i, s] - c[s]))``.
+        ``c``: the result of :meth:`mixis_draw_lse` (computed when None); the slots of ``agg`` are documented in
+        include/pyloo_amd.h."""
+        a, n, s, so, sd, code, space, stream, device = self._mixis_input(ll)
+        if c is None:
+            c = self.mixis_draw_lse(ll)["c"]
+        elif device is None:
+            c = np.ascontiguousarray(c, dtype=np.float64)
+        else:
+            import torch
+
+            c = torch.as_tensor(c, dtype=torch.float64, device=device).contiguous()
+        if c.shape != (s,):
+            raise ValueError(f"c must have one entry per draw: expected ({s},), got {tuple(c.shape)}")
+        loo_i = self._mixis_new(n, device) if pointwise else None
+        agg = self._mixis_new(AGG_COUNT, device) if aggregate else None
+        p = self._mixis_ptr
+        check(self._lib.pla_mixis_loo(self._h, p(a), code, n, s, so, sd, p(c), float(scale_value), space, stream, p(loo_i), p(agg)))
+        return {"loo_i": loo_i, "c": c, "agg": agg}
+
+    def set_mixis_grid(self, max_workgroups):
+        """Cap the workgroups per launch of the Mix-IS-LOO passes (0: the library's choice); the results do not depend on it."""
+        check(self._lib.pla_engine_set_mixis_grid(self._h, int(max_workgroups)))
+
+    @staticmethod
+    def mixis_tile_rows(n_obs):
+        """Rows per partial of pass 1 for ``n_obs`` observations (``pla_mixis_tile_rows``)."""
+        rc = load_library().pla_mixis_tile_rows(int(n_obs))
+        if rc < 0:
+            check(rc)
+        return rc
+
     # ------------------------------------------------------------------ weighted expectations
     def e_loo(self, x, log_weights, log_ratios=None, tail_len=20):
         """(n_obs, n_draws) draws ``x`` + log-weights (+ raw log ratios) -> ``dict(mean, var, k_mean, k_var, k_none)``

@@ -4,8 +4,8 @@ object (pyloo/loo.py:20-513), executed by the HIP engine.
 What runs where: argument handling, warnings and ``ELPDData`` packing are host Python (they
 follow loo.py:179-249,291-304,344-412); everything between ``compute_importance_weights`` and
 the final sums (loo.py:286-342: three Python loops over observations in the reference) is one
-``pla_psis_loo`` call.  ``mixture=True`` and ``moment_match=True`` are outside this project's
-scope and raise ``NotImplementedError``.
+``pla_psis_loo`` call.  ``mixture=True`` raises ``NotImplementedError`` here: Mix-IS-LOO is ``loo_mixture()``
+(loo_mixture.py).  ``moment_match=True`` is outside this project's scope and raises it too.
 """
 
 import warnings
@@ -207,7 +207,7 @@ def loo(data, pointwise=None, var_name=None, reff=None, scale=None, method="psis
     method = _checked_method(method)  # loo.py:229-244
     good_k = min(1 - 1 / np.log10(n_samples), 0.7)  # loo.py:249
     if mixture:
-        raise NotImplementedError("mixture=True (Mix-IS-LOO, loo.py:252-284) is outside the scope of pyloo_amd")
+        raise NotImplementedError("mixture=True (Mix-IS-LOO, loo.py:252-284) is a separate entry point: use pl.loo_mixture")
     if moment_match:
         if not pointwise:
             raise ValueError(
