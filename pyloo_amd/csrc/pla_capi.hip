@@ -2057,6 +2057,7 @@ static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, 
   hipStream_t s = (hipStream_t)stream;
   const size_t esz = dtype == PLA_F64 ? 8 : 4;
   PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));  // [1]: replaced entries
+  eng->last_kernels.clear();  // (no observations: nothing is launched)
 
   if (mem_space == PLA_DEVICE) {
     double *dl = lppd_i, *dv = var_i, *dw = waic_i;
@@ -2073,6 +2074,7 @@ static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, 
       // observations-fastest matrix, read in place: one lane per observation (pla_waic.h)
       TimedLaunch t(eng, s);
       PLA_HIP(pla::launch_waic_col(ll, dtype, n_obs, (int)n_draws, stride_draw, scale_value, dl, dv, dw, eng->counters + 1, s));
+      eng->last_kernels = pla::last_rows_kernels();
     } else if (obs_fastest_device(mem_space, row_index, n_src, n_draws, stride_obs, stride_draw)) {
       const int64_t rows_per_chunk = staged_chunk_rows(mem_space, true, n_obs, n_draws, esz);
       rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)rows_per_chunk * (size_t)n_draws * esz);
@@ -2083,6 +2085,7 @@ static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, 
         PLA_HIP(pla::launch_transpose_rows(ll, dtype, stride_draw, r0, nr, (int)n_draws, eng->d_in, s));
         PLA_HIP(pla::launch_waic(eng->d_in, nullptr, dtype, nr, (int)n_draws, n_draws, 1, scale_value, dl ? dl + r0 : nullptr,
                                  dv ? dv + r0 : nullptr, dw ? dw + r0 : nullptr, eng->counters + 1, s));
+        eng->last_kernels = std::string("transpose_rows_kernel + ") + pla::last_rows_kernels();
       }
     } else {
       TimedLaunch t(eng, s);
@@ -2093,6 +2096,7 @@ static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, 
       }
       PLA_HIP(pla::launch_waic(ll, rows_d, dtype, n_obs, (int)n_draws, stride_obs, stride_draw, scale_value, dl, dv, dw,
                                eng->counters + 1, s));
+      eng->last_kernels = pla::last_rows_kernels();
     }
     if (agg) {
       pla::ReduceParams rp{dv, dw, dv, n_obs, 0.4, agg, eng->counters + 1};  // waic.py:147 threshold
@@ -2130,6 +2134,7 @@ static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, 
       TimedLaunch t(eng, s);
       PLA_HIP(pla::launch_waic(eng->d_in, nullptr, dtype, nr, (int)n_draws, n_draws, 1, scale_value, dl + r0, dv + r0, dw + r0,
                                eng->counters + 1, s));
+      eng->last_kernels = std::string(pla::last_rows_kernels()) + " (blocks of observations uploaded)";
     }
     PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next chunk
   }

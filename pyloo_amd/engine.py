@@ -1008,7 +1008,10 @@ class Engine:
         return ms.value, k.value
 
     def last_kernels(self):
-        """Which kernels the last PSIS-LOO / weights / group / e_loo call launched (text; for benchmark records and tests)."""
+        """Which kernels the last PSIS-LOO / weights / group / e_loo / WAIC call launched (text; for benchmark records and
+        tests).  After ``waic``: ``waic_wave_kernel<T, W>``, ``waic_rows_kernel<T>`` or ``waic_col_kernel<T>``, behind
+        ``transpose_rows_kernel + `` on the ``PLA_INGEST_TRANSPOSE`` path and followed by ``(blocks of observations uploaded)``
+        for a host matrix."""
         buf = C.create_string_buffer(512)
         check(self._lib.pla_engine_last_kernels(self._h, buf, 512))
         return buf.value.decode("utf-8", "replace")

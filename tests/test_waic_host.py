@@ -104,3 +104,59 @@ def test_several_log_likelihoods(ll8):  # test_waic.py:63-70
     with pytest.raises(TypeError, match="Found several log likelihood arrays"):
         pl.waic(d)
     assert pl.waic(d, var_name="obs") is not None
+
+
+# ------------------------------------------------------------------------------------------------ tests/waic_ref.py
+REF_KEYS = ("lppd_i", "var_i", "waic_i", "elpd_waic", "se", "p_waic")
+
+
+def _golden_cases():
+    import cases
+
+    return [c[0] for c in cases.CASES]
+
+
+@pytest.mark.parametrize("case", _golden_cases())
+def test_waic_ref_against_oracle(case, golden):
+    """The wide restatement of tests/waic_ref.py against the oracle on every golden matrix (edge rows included)."""
+    from waic_ref import waic_ref
+
+    ll = golden(case)["ll"]
+    got, want = waic_ref(ll, 1.0), orc.waic_arrays(ll.astype(np.float64), 1)
+    for key in REF_KEYS:
+        np.testing.assert_allclose(got[key], want[key], rtol=1e-13, atol=1e-13, err_msg=key)
+    assert got["n_high"] == int(np.sum(want["var_i"] > 0.4))
+    assert (got["n_nan"] > 0) == want["has_nan"] and (got["n_inf"] > 0) == want["has_inf"]
+    assert got["n_nan"] == int(np.isnan(ll).sum()) and got["n_inf"] == int(np.isinf(ll).sum())
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_waic_ref_float64_against_wide(dtype):
+    from waic_ref import waic_ref
+
+    rng = np.random.default_rng(260)
+    ll = (-rng.uniform(0.05, 1.2, size=(64, 1)) * rng.exponential(size=(64, 260)) + rng.normal(size=(64, 1))).astype(dtype)
+    wide, plain = waic_ref(ll, -2.0, wide=True), waic_ref(ll, -2.0, wide=False)
+    for key in REF_KEYS:
+        np.testing.assert_allclose(plain[key], wide[key], rtol=1e-13, atol=1e-13, err_msg=key)
+    assert plain["n_high"] == wide["n_high"] and plain["n_nan"] == plain["n_inf"] == 0
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_waic_ref_counts_and_replacements(dtype):
+    from waic_ref import sanitise, waic_ref
+
+    rng = np.random.default_rng(7)
+    ll = (-0.4 * rng.exponential(size=(6, 40)) - 2.0).astype(dtype)
+    ll[0, 3], ll[0, 39], ll[2, 0] = np.nan, np.nan, np.nan
+    ll[1, 5], ll[3, 7], ll[3, 8], ll[4, :] = np.inf, -np.inf, np.inf, -np.inf
+    for wide in (True, False):
+        res = waic_ref(ll, 1.0, wide=wide)
+        assert res["n_nan"] == int(np.isnan(ll).sum()) == 3 and res["n_inf"] == int(np.isinf(ll).sum()) == 43
+    x, _, _ = sanitise(ll)
+    assert x.dtype == dtype and np.all(np.isfinite(x))
+    assert x[0, 3] == -1e10 and x[1, 5] == 1e10 and x[3, 7] == -1e10 and np.all(x[4] == -1e10)
+    fin = np.isfinite(ll)
+    np.testing.assert_array_equal(x[fin], ll[fin])
+    # a row of nothing but replacements: constant, so lppd_i is the constant and the variance is exactly 0
+    assert res["lppd_i"][4] == -1e10 and res["var_i"][4] == 0.0
