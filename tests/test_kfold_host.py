@@ -1,4 +1,5 @@
-"""Host side of ``loo_kfold`` without a GPU: the splitters against the reference's fold arrays, the front against the reference's
+"""Host side of ``loo_kfold`` without a GPU: the yardstick of the GPU task tests (tests/kfold_ref.py) against the goldens and the
+oracle, the splitters against the reference's fold arrays, the front against the reference's
 numbers through an oracle-backed stand-in engine, its errors and warnings, the ``ELPDData`` it builds and prints, ``loo_compare`` on
 k-fold results, the two C entry points and the generated code of the new kernels."""
 
@@ -65,6 +66,39 @@ def gold():
 def case_inputs(gold, case):
     K = int(gold[f"{case}/K"])
     return gold[f"{case}/ll_full"], [gold[f"{case}/fold_{k + 1}"] for k in range(K)], gold[f"{case}/folds"], str(gold[f"{case}/scale"])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the yardstick
+@pytest.mark.parametrize("case", CASES)
+def test_lme_ref_against_goldens_and_oracle(gold, case):
+    """tests/kfold_ref.py (the yardstick of tests/test_gpu_kfold_tasks.py) on every golden case: against the reference's stored
+    vectors and against the oracle on the f64 widening, at the project's log-mean-exp tolerances, NaN in the same places."""
+    from kfold_ref import lme_ref
+
+    full, mats, folds, _ = case_inputs(gold, case)
+    n = full.shape[0]
+    lpd, n_rep = lme_ref(full, nan_fix=True)
+    assert n_rep.sum() == int(gold[f"{case}/n_nan"]) == np.isnan(full).sum()
+    elpd = np.zeros(n)
+    held = [None] * n  # observation i's row under the fit that left it out
+    for k, m in enumerate(mats):
+        idx = np.where(folds == k + 1)[0]
+        rows = m[idx] if m.shape[0] == n else m
+        elpd[idx], n_rep = lme_ref(rows, nan_fix=False)
+        assert n_rep.sum() == 0
+        for i, r in zip(idx, rows):
+            held[i] = r
+    with np.errstate(all="ignore"):
+        o_lpd = np.array([orc.lse(np.where(np.isnan(r), -1e10, r).astype(np.float64), b_inv=r.size) for r in full])
+        o_elpd = np.array([orc.lse(r.astype(np.float64), b_inv=r.size) for r in held])
+    for got, stored, oracle in ((lpd, gold[f"{case}/lpd_full"], o_lpd), (elpd, gold[f"{case}/elpd"], o_elpd)):
+        for want in (stored, oracle):
+            np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
+            np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-12, equal_nan=True)
+    # without the flag a NaN of the full fit stays
+    raw, n_rep = lme_ref(full, nan_fix=False)
+    assert n_rep.sum() == 0
+    np.testing.assert_array_equal(np.isnan(raw), np.isnan(full).any(axis=1) | np.isnan(lpd))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the splitters
