@@ -502,6 +502,37 @@ int pla_engine_set_nonfactor_route(pla_engine *eng, int route);
 int pla_engine_set_nonfactor_grid(pla_engine *eng, int max_workgroups);
 int pla_nonfactor_lds_max_obs(void);
 
+/*
+ * LOO-PIT, the leave-one-out probability integral transform (ArviZ's loo_pit; csrc/pla_pit.h), per observation i:
+ *     pit_le[i] = sum_{y_hat[i,s] <= y[i]} w[i,s]        pit_lt[i] = sum_{y_hat[i,s] < y[i]} w[i,s]
+ * with w[i,.] the normalised leave-one-out weights of observation i and y_hat[i,.] its posterior-predictive draws.  `in` and y_hat
+ * are (n_obs, n_draws) matrices of one dtype, each with its own strides (elements); y is [n_obs] doubles.
+ *   PLA_PIT_LOGLIK       in = pointwise log-likelihood.  One block of observations at a time (PLA_INGEST_BLOCK_MB, as
+ *                        pla_psis_loo_draws sizes its blocks): -in with NaN -> -1e10 (counted in *n_replaced) into the ingest
+ *                        staging, the weights pass of pla_importance_weights (method, tail_count) into a second bounded buffer,
+ *                        the PIT kernel against y_hat -- read in place, or, observations fastest, transposed block by block
+ *                        into a third.  diag[n_obs] (may be NULL) receives the Pareto k of PLA_PSIS.  The results do not depend
+ *                        on the block size, bitwise.
+ *   PLA_PIT_LOG_WEIGHTS  in = log weights of any normalisation (psislw's output): used as they are, w = softmax over the draws;
+ *                        method, tail_count and diag are ignored, *n_replaced = 0.  Device pointers: the PIT kernel alone, both
+ *                        matrices read in place.
+ * All arithmetic is f64; comparisons are IEEE (a NaN draw or a NaN y[i] is never counted), a weight of log -inf is 0, a row whose
+ * weights are all NaN or all -inf gives NaN.  The three sums behind the two values take one term per draw in one fixed order:
+ * pit_lt[i] == pit_le[i] bit for bit when no draw equals y[i], exactly 1 when every draw is <= y[i], exactly 0 when none is; the
+ * same input gives the same bits on every call.
+ * PLA_DEVICE: everything is enqueued on `stream`, the outputs and n_replaced (one int64) are device pointers, and nothing is
+ * allocated once the workspace fits (pla_engine_set_frozen).  PLA_HOST: each matrix draws-fastest (unit draw stride) or
+ * observations-fastest (unit observation stride, draw stride >= n_obs), staged in 1 GiB blocks; other strides return
+ * PLA_ERR_UNSUPPORTED.  pit_lt, diag and n_replaced may be NULL.  PLA_ERR_ARG: a NULL matrix, y or pit_le, n_draws < 2, a bad
+ * kind or method, a stride that is not positive.
+ */
+#define PLA_PIT_LOGLIK 0       /* in = pointwise log-likelihood: weights = PSIS/SIS/TIS of -in (NaN -> -1e10) */
+#define PLA_PIT_LOG_WEIGHTS 1  /* in = log weights of any normalisation (e.g. psislw's output): used as they are */
+int pla_loo_pit(pla_engine *eng, const void *in, const void *y_hat, const double *y, int dtype, int64_t n_obs, int64_t n_draws,
+                int64_t stride_obs, int64_t stride_draw, int64_t yh_stride_obs, int64_t yh_stride_draw, int input_kind, int method,
+                int64_t tail_count, int mem_space, void *stream, double *pit_le, double *pit_lt /* may be NULL */,
+                double *diag /* may be NULL; written only for PLA_PIT_LOGLIK */, int64_t *n_replaced /* may be NULL */);
+
 /* Timing of the dominant kernel, measured with hipEvents on the launch stream.
  * enable != 0 brackets every main-kernel launch with events; pla_engine_kernel_ms returns the
  * accumulated milliseconds and launch count since the last call (it synchronises the events). */

@@ -14,6 +14,7 @@ AGG_N, AGG_SUM_LOO, AGG_M2_LOO, AGG_SUM_LPPD, AGG_N_HIGH, AGG_N_NONFINITE, AGG_M
 AGG_COUNT = 8
 ABI_VERSION = 7
 PLA_MVN_NORMAL, PLA_MVN_STUDENT_T = 0, 1
+PLA_PIT_LOGLIK, PLA_PIT_LOG_WEIGHTS = 0, 1  # input_kind of pla_loo_pit
 PLA_NONFACTOR_MAX_OBS = 1024
 # status word of a draw of pla_nonfactor_loglik
 NF_GENERAL, NF_SINGULAR, NF_NONFINITE, NF_DF_NONPOS, NF_BETA_NONFINITE, NF_CLAMPED = 1, 2, 4, 8, 16, 32
@@ -34,6 +35,7 @@ SYMBOLS = (
     "pla_kfold_lme", "pla_kfold_reduce",
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
+    "pla_loo_pit",
 )
 
 
@@ -119,6 +121,7 @@ def load_library():
     lib.pla_mixis_loo.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, dbl, ci, vp, vp, vp]
     lib.pla_engine_set_mixis_grid.argtypes = [vp, ci]
     lib.pla_mixis_tile_rows.argtypes = [i64]
+    lib.pla_loo_pit.argtypes = [vp, vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, i64, ci, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

@@ -105,6 +105,8 @@ struct pla_engine {
   void* d_mix = nullptr;  // Mix-IS-LOO (pla_mixis.h): the slab of pass 1, c, the unscaled pointwise values, the finishing pass's partials
   size_t d_mix_bytes = 0;
   int mixis_grid = 0;  // pla_engine_set_mixis_grid (0: the library's choice)
+  void* d_pit = nullptr;  // LOO-PIT (pla_pit.h): one block of predictive draws, draws fastest (transposed or staged from the host)
+  size_t d_pit_bytes = 0;
   std::string kf_label;  // the routes of the last pla_kfold_lme, for the text pla_kfold_reduce leaves in last_kernels
   int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
   int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
@@ -373,6 +375,7 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_kf) (void)hipFree(e->d_kf);
   if (e->d_mm) (void)hipFree(e->d_mm);
   if (e->d_mix) (void)hipFree(e->d_mix);
+  if (e->d_pit) (void)hipFree(e->d_pit);
   for (int i = 0; i < 2; ++i) {
     if (e->h_kf[i]) (void)hipHostFree(e->h_kf[i]);
     if (e->kf_event[i]) (void)hipEventDestroy(e->kf_event[i]);
@@ -2040,6 +2043,193 @@ int pla_importance_weights(pla_engine* eng, const void* logw, int dtype, int64_t
   }
   if (diag) PLA_HIP(hipMemcpyAsync(diag, eng->d_pw, n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
   PLA_HIP(hipStreamSynchronize(s));
+  return PLA_OK;
+}
+
+// ---- LOO-PIT (csrc/pla_pit.h) ---------------------------------------------------------------------------------------------------
+int pla_loo_pit(pla_engine* eng, const void* in, const void* y_hat, const double* y, int dtype, int64_t n_obs, int64_t n_draws,
+                int64_t stride_obs, int64_t stride_draw, int64_t yh_stride_obs, int64_t yh_stride_draw, int input_kind, int method,
+                int64_t tail_count, int mem_space, void* stream, double* pit_le, double* pit_lt, double* diag, int64_t* n_replaced) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (input_kind != PLA_PIT_LOGLIK && input_kind != PLA_PIT_LOG_WEIGHTS) return fail(PLA_ERR_ARG, "bad input_kind");
+  if (method != PLA_PSIS && method != PLA_SIS && method != PLA_TIS) return fail(PLA_ERR_ARG, "bad method");
+  if (n_obs < 0) return fail(PLA_ERR_ARG, "n_obs < 0");
+  if (n_draws < 2 || n_draws > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_draws out of range (at least 2)");
+  if (stride_obs <= 0 || stride_draw <= 0 || yh_stride_obs <= 0 || yh_stride_draw <= 0) return fail(PLA_ERR_ARG, "strides must be positive");
+  if (n_obs > 0 && (!in || !y_hat || !y || !pit_le)) return fail(PLA_ERR_ARG, "in / y_hat / y / pit_le is NULL");
+  const bool loglik = input_kind == PLA_PIT_LOGLIK;
+  if (loglik) {
+    const int rc0 = check_common(eng, in, dtype, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, mem_space);
+    if (rc0) return rc0;
+  }
+  const bool host = mem_space == PLA_HOST;
+  const bool in_of = host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw);
+  const bool yh_of = host_obs_fastest(n_obs, n_draws, yh_stride_obs, yh_stride_draw);
+  if (host && ((stride_draw != 1 && !in_of) || (yh_stride_draw != 1 && !yh_of)))
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST matrices need unit stride along the draws, or along the observations");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_obs == 0) {
+    if (host && n_replaced) *n_replaced = 0;
+    if (!host && n_replaced) PLA_HIP(hipMemsetAsync(n_replaced, 0, sizeof(int64_t), s));
+    return PLA_OK;
+  }
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int S = (int)n_draws;
+  char route[160], prep_text[96] = "";
+  int rc;
+
+  // ---- log weights on the device: the PIT kernel alone, both matrices in place
+  if (!loglik && !host) {
+    PLA_HIP(pla::launch_pit(in, y_hat, y, dtype, n_obs, S, stride_obs, stride_draw, yh_stride_obs, yh_stride_draw, pit_le, pit_lt, s,
+                            route, (int)sizeof(route)));
+    if (n_replaced) PLA_HIP(hipMemsetAsync(n_replaced, 0, sizeof(int64_t), s));
+    eng->last_kernels = std::string(route) + " (matrices read in place)";
+    return PLA_OK;
+  }
+
+  // ---- the weights pass of a block, as pla_importance_weights sets it up
+  pla::RowsParams p{};
+  p.n_draws = S;
+  p.method = method;
+  p.tail_count = method == PLA_PSIS ? (int)tail_count : 0;
+  p.tail_cap = pow2_at_least(p.tail_count);
+  p.scale_value = 1.0;
+  p.counters = eng->counters;
+  p.stride_obs = n_draws;
+  p.stride_draw = 1;
+  // rows per block: the ingest staging's size on the device, 1 GiB from the host; long rows keep the split weights route and its
+  // 2^17-row inner blocks (pla_importance_weights)
+  int64_t rows = staged_chunk_rows(mem_space, true, n_obs, n_draws, esz);
+  const bool split = loglik && method == PLA_PSIS && n_draws > 4096 && tail_count <= 448;
+  if (split && rows > ((int64_t)1 << 17)) rows = (int64_t)1 << 17;
+  const size_t block_bytes = (size_t)rows * (size_t)n_draws * esz;
+  if (loglik) {
+    PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));
+    rc = grow(&eng->d_slow, &eng->d_slow_bytes, (size_t)rows * sizeof(unsigned));
+    if (rc) return rc;
+    p.slow_list = (unsigned*)eng->d_slow;
+    if (method == PLA_PSIS) {
+      rc = ensure_l1_table(eng, tail_count, s, &p.l1_table);
+      if (rc) return rc;
+    }
+    if (split) {
+      const int stride = (int)((tail_count + 63) & ~(int64_t)63);
+      rc = grow(&eng->d_ws, &eng->d_ws_bytes, (size_t)rows * (size_t)(stride + 8) * sizeof(double));
+      if (rc && rc != PLA_ERR_NOMEM) return rc;
+      if (!rc) {  // (no room: the fused weights kernel, which needs none)
+        p.ws_y = (double*)eng->d_ws;
+        p.ws_s = p.ws_y + (size_t)rows * stride;
+        p.ws_stride = stride;
+        p.ws_sstride = 8;
+        p.lw_split = true;
+      }
+    }
+    rc = grow(&eng->d_lw, &eng->d_lw_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  if (loglik || host) {
+    rc = grow(&eng->d_in, &eng->d_in_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  const bool yh_transpose = host ? yh_of : obs_fastest_device(mem_space, nullptr, n_obs, n_draws, yh_stride_obs, yh_stride_draw);
+  if (host || yh_transpose) {
+    rc = grow(&eng->d_pit, &eng->d_pit_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  if (host && (in_of || yh_of)) {
+    rc = grow(&eng->d_slab, &eng->d_slab_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  unsigned long long* d_count = nullptr;
+  const double* dy = y;
+  double *d_le = pit_le, *d_lt = pit_lt, *d_diag = loglik ? diag : nullptr;
+  if (host) {
+    size_t have_b = eng->d_pw_elems * sizeof(double);
+    rc = grow((void**)&eng->d_pw, &have_b, (size_t)(4 * n_obs + PLA_AGG_COUNT) * sizeof(double));
+    eng->d_pw_elems = have_b / sizeof(double);
+    if (rc) return rc;
+    PLA_HIP(hipMemcpyAsync(eng->d_pw, y, (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, s));
+    dy = eng->d_pw;
+    d_le = eng->d_pw + n_obs;
+    d_lt = eng->d_pw + 2 * n_obs;
+    d_diag = eng->d_pw + 3 * n_obs;
+    d_count = eng->counters + pla::kCounterPitReplaced;
+    PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  } else {
+    d_count = (unsigned long long*)n_replaced;
+    if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+  }
+
+  std::string label;
+  const size_t row_bytes = (size_t)n_draws * esz;
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+    const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+    // the weights' source as a compact draws-fastest block in d_in (log-likelihood: negated, NaN -> -1e10)
+    const void* lw_block = eng->d_in;
+    const char* prep = "";
+    if (!host) {
+      PLA_HIP(pla::launch_pit_prepare((const char*)in + (size_t)r0 * (size_t)stride_obs * esz, dtype, stride_obs, stride_draw, nr, S,
+                                      eng->d_in, d_count, s, &prep));
+    } else if (in_of) {  // the (n_draws, nr) slab as it lies, turned on the device
+      PLA_HIP(hipMemcpy2DAsync(eng->d_slab, (size_t)nr * esz, (const char*)in + (size_t)r0 * esz, (size_t)stride_draw * esz,
+                               (size_t)nr * esz, (size_t)n_draws, hipMemcpyHostToDevice, s));
+      if (loglik) PLA_HIP(pla::launch_pit_prepare(eng->d_slab, dtype, 1, nr, nr, S, eng->d_in, d_count, s, &prep));
+      else PLA_HIP(pla::launch_transpose_rows(eng->d_slab, dtype, nr, 0, nr, S, eng->d_in, s));
+    } else {
+      void* up = loglik ? eng->d_lw : eng->d_in;  // (the weights buffer is free until the weights pass writes it)
+      PLA_HIP(hipMemcpy2DAsync(up, row_bytes, (const char*)in + (size_t)r0 * (size_t)stride_obs * esz, (size_t)stride_obs * esz, row_bytes,
+                               (size_t)nr, hipMemcpyHostToDevice, s));
+      if (loglik) PLA_HIP(pla::launch_pit_prepare(eng->d_lw, dtype, n_draws, 1, nr, S, eng->d_in, d_count, s, &prep));
+    }
+    if (loglik) {
+      p.in = eng->d_in;
+      p.n_obs = nr;
+      p.diag = d_diag ? d_diag + r0 : nullptr;
+      p.lw_out = eng->d_lw;
+      PLA_HIP(pla::launch_rows(p, dtype, true, s));
+      lw_block = eng->d_lw;
+    }
+    // the predictive draws of the block: in place, or draws fastest in d_pit
+    const void* yh_block = (const char*)y_hat + (size_t)r0 * (size_t)yh_stride_obs * esz;
+    int64_t yso = yh_stride_obs, ysd = yh_stride_draw;
+    if (host && yh_of) {
+      PLA_HIP(hipMemcpy2DAsync(eng->d_slab, (size_t)nr * esz, (const char*)y_hat + (size_t)r0 * esz, (size_t)yh_stride_draw * esz,
+                               (size_t)nr * esz, (size_t)n_draws, hipMemcpyHostToDevice, s));
+      PLA_HIP(pla::launch_transpose_rows(eng->d_slab, dtype, nr, 0, nr, S, eng->d_pit, s));
+    } else if (host) {
+      PLA_HIP(hipMemcpy2DAsync(eng->d_pit, row_bytes, yh_block, (size_t)yh_stride_obs * esz, row_bytes, (size_t)nr, hipMemcpyHostToDevice, s));
+    } else if (yh_transpose) {
+      PLA_HIP(pla::launch_transpose_rows(y_hat, dtype, yh_stride_draw, r0, nr, S, eng->d_pit, s));
+    }
+    if (host || yh_transpose) {
+      yh_block = eng->d_pit;
+      yso = n_draws;
+      ysd = 1;
+    }
+    PLA_HIP(pla::launch_pit(lw_block, yh_block, dy + r0, dtype, nr, S, n_draws, 1, yso, ysd, d_le + r0, d_lt ? d_lt + r0 : nullptr, s, route,
+                            (int)sizeof(route)));
+    if (r0 == 0) {
+      snprintf(prep_text, sizeof(prep_text), "%s", prep);
+      label = std::string(prep_text[0] ? prep_text : (in_of && host ? "transpose_rows_kernel" : "rows copied")) +
+              (loglik ? " -> " + std::string(pla::last_rows_kernels()) : std::string()) +
+              (yh_transpose ? " + transpose_rows_kernel (y_hat)" : "") + " -> " + route +
+              (host ? " (matrices staged in blocks)" : " per block of observations");
+    }
+    if (host) PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+  }
+  eng->last_kernels = label;
+  if (!host) return PLA_OK;
+  PLA_HIP(hipMemcpyAsync(pit_le, d_le, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (pit_lt) PLA_HIP(hipMemcpyAsync(pit_lt, d_lt, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (diag && loglik) PLA_HIP(hipMemcpyAsync(diag, d_diag, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+  unsigned long long h = 0;
+  PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h;
   return PLA_OK;
 }
 

@@ -208,6 +208,14 @@ hipError_t launch_mixis_elpd(const void* in, int dtype, int64_t n_obs, int n_dra
                              hipStream_t stream, char* route, int cap);
 // agg[PLA_AGG_N_SLOW] = replaced[0] + replaced[1], agg[PLA_AGG_N_NONFINITE] = 0 (agg may be null); counts[2] = replaced (may be null)
 hipError_t launch_mixis_counts(const unsigned long long* replaced, double* agg, int64_t* counts, hipStream_t stream);
+// LOO-PIT (pla_pit.h).  launch_pit_prepare: out (n_rows, n_draws) contiguous = -in with NaN -> -1e10 (counted in `replaced`, may be
+// null), `in` read with its own strides.  launch_pit: pit_le[r] / pit_lt[r] (pit_lt may be null) from the log weights, the draws
+// yh (the dtype of lw) and y, each matrix with its own strides; route: text for pla_engine_last_kernels.
+hipError_t launch_pit_prepare(const void* in, int dtype, int64_t stride_obs, int64_t stride_draw, int64_t n_rows, int n_draws, void* out,
+                              unsigned long long* replaced, hipStream_t stream, const char** route);
+hipError_t launch_pit(const void* lw, const void* yh, const double* y, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs,
+                      int64_t lw_stride_draw, int64_t yh_stride_obs, int64_t yh_stride_draw, double* pit_le, double* pit_lt,
+                      hipStream_t stream, char* route, int cap);
 // moment matching (pla_mm.h): batched moments, affine transform and ratio assembly, f64, device memory
 constexpr int kMmMaxCovDim = 64;  // D with matrices (moments with cov, transform with a matrix)
 constexpr int kMmMaxDim = 1024;   // D without

@@ -784,6 +784,56 @@ class Engine:
                                   *(p(out[k]) for k in ("mean", "var", "k_mean", "k_var", "k_none"))))
         return out
 
+    # ------------------------------------------------------------------ LOO-PIT
+    def loo_pit(self, mat, y_hat, y, tail_count=0, method="psis", kind="loglik"):
+        """(n_obs, n_draws) log-likelihood (``kind="loglik"``) or log weights (``kind="log_weights"``), the predictive draws
+        ``y_hat`` of the same shape and the observed ``y`` [n_obs] -> ``dict(pit_le, pit_lt, diag, n_replaced)`` (``pla_loo_pit``).
+        The two matrices are promoted to one dtype (f64 if either is) and passed with their own strides.  NumPy in -> NumPy out
+        (and an int); CUDA tensors in -> CUDA tensors out, nothing synchronised.  ``diag`` is None for log weights."""
+        mcode = METHOD_CODES[method]
+        if kind not in ("loglik", "log_weights"):
+            raise ValueError(f"kind must be 'loglik' or 'log_weights', got {kind!r}")
+        kcode = _capi.PLA_PIT_LOGLIK if kind == "loglik" else _capi.PLA_PIT_LOG_WEIGHTS
+        if _is_torch_tensor(mat):
+            import torch
+
+            if not _is_torch_tensor(y_hat) or mat.dim() != 2 or y_hat.shape != mat.shape or not mat.is_cuda or not y_hat.is_cuda:
+                raise ValueError("mat and y_hat must be 2-D CUDA tensors of one shape")
+            dt = torch.float64 if torch.float64 in (mat.dtype, y_hat.dtype) else torch.float32
+            mats = [m.to(dt) for m in (mat, y_hat)]
+            mats = [m if min(m.stride()) > 0 else m.contiguous() for m in mats]
+            n, s = mats[0].shape
+            dev = mats[0].device
+            yv = torch.as_tensor(y, device=dev).to(torch.float64).reshape(-1).contiguous()
+            if yv.numel() != n:
+                raise ValueError(f"y has {yv.numel()} values for {n} observations")
+            pit_le, pit_lt = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+            diag = torch.empty(n, dtype=torch.float64, device=dev) if kind == "loglik" else None
+            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
+            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            code = _capi.PLA_F64 if dt == torch.float64 else _capi.PLA_F32
+            check(self._lib.pla_loo_pit(self._h, p(mats[0]), p(mats[1]), p(yv), code, n, s, mats[0].stride(0), mats[0].stride(1),
+                                        mats[1].stride(0), mats[1].stride(1), kcode, mcode, int(tail_count), PLA_DEVICE, self._stream(),
+                                        p(pit_le), p(pit_lt), p(diag), p(nrep)))
+            return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": nrep}
+        mats = [np.asarray(mat), np.asarray(y_hat)]
+        if mats[0].ndim != 2 or mats[1].shape != mats[0].shape:
+            raise ValueError("mat and y_hat must be 2-D arrays of one shape")
+        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
+        mats = [self._as_2d_host(m if m.dtype == dt else m.astype(dt), allow_obs_fastest=True) for m in mats]
+        n, s = mats[0].shape
+        yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+        if yv.size != n:
+            raise ValueError(f"y has {yv.size} values for {n} observations")
+        (so, sd), (yso, ysd) = self._host_strides(mats[0]), self._host_strides(mats[1])
+        pit_le, pit_lt = np.empty(n), np.empty(n)
+        diag = np.empty(n) if kind == "loglik" else None
+        nrep = C.c_int64(0)
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        check(self._lib.pla_loo_pit(self._h, p(mats[0]), p(mats[1]), p(yv), dtype_code(dt), n, s, so, sd, yso, ysd, kcode, mcode,
+                                    int(tail_count), PLA_HOST, None, p(pit_le), p(pit_lt), p(diag), C.byref(nrep)))
+        return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": int(nrep.value)}
+
     def e_loo_quantiles(self, x, log_weights, probs):
         """(n_obs, n_draws) draws + log-weights, quantile levels -> (n_obs, n_probs) weighted quantiles (``pla_e_loo_quantiles``:
         e_loo.py:468-515, 534-554)."""
