@@ -533,6 +533,44 @@ int pla_loo_pit(pla_engine *eng, const void *in, const void *y_hat, const double
                 int64_t tail_count, int mem_space, void *stream, double *pit_le, double *pit_lt /* may be NULL */,
                 double *diag /* may be NULL; written only for PLA_PIT_LOGLIK */, int64_t *n_replaced /* may be NULL */);
 
+/*
+ * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
+ * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
+ * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):
+ *     lr_j[s] = sum_{r = first}^{first + j - 1} ll[r, s]            f_j[s] = ll[first + j, s] + ... + ll[first + j + horizon - 1, s]
+ *     j = 0:  elpd_i[0] = logsumexp_s(f_0) - log n_draws, diag[0] = 0  (the fit's own step: exact, no importance sampling)
+ *     j > 0:  (lw_j, diag[j]) = PSIS(lr_j) with tail_count, as pla_importance_weights;
+ *             elpd_i[j] = logsumexp_s(lw_j + f_j) - logsumexp_s(lw_j)
+ * All arithmetic is f64 (f32 input is widened on load); NaN entries of ll count as -1e10 and are counted in *n_replaced (pla_lfo:
+ * every entry of rows [first, first + n_steps + horizon - 1) once; pla_lfo_ratios: of rows [first, first + n_steps - 1)); +-inf are
+ * kept.  A weight of log -inf is 0; a step whose weights are all NaN gives NaN.
+ *
+ * THE SUMMATION RULE of lr.  With the chunk length C = 64, per draw, every sum taken in the order written:
+ *     total[c] = ll[first + cC] + ll[first + cC + 1] + ... + ll[first + cC + C - 1]        carry[0] = 0, carry[c + 1] = carry[c] + total[c]
+ *     local[j] = 0 when j is a multiple of C, else ll[first + cC] + ... + ll[first + j - 1] with c = j / C       lr_j = carry[j / C] + local[j]
+ * It depends on j and C alone: the results have the same bits whatever the grid, the block size (PLA_INGEST_BLOCK_MB: the call works
+ * one block of whole chunks at a time -- ratios into the ingest staging, the weights pass into a second bounded buffer, the predict
+ * kernel before the next block overwrites either), the layout and the memory space.  No floating-point atomics.
+ *
+ * pla_lfo_ratios  out (n_steps, n_draws) C-contiguous, ALWAYS f64: out[j, s] = lr_j[s] (row 0 is all zeros).
+ *                 1 <= n_steps <= n_obs - first + 1.
+ * pla_lfo         diag, elpd_i [n_steps] (each may be NULL).  *first_high (may be NULL) = the smallest j >= 1 with
+ *                 diag[j] > k_threshold, or n_steps when there is none (a NaN k is not above).  Needs first >= 0, horizon >= 1,
+ *                 1 <= n_steps <= n_obs - first - horizon + 1, n_draws >= 2 and a tail_count pla_importance_weights accepts
+ *                 (PLA_ERR_ARG otherwise); method PLA_PSIS only (PLA_SIS / PLA_TIS: PLA_ERR_UNSUPPORTED).
+ * Layouts, in either memory space: draws fastest (stride_draw == 1, any stride_obs >= n_draws: read in place on the device), or
+ * observations fastest (stride_obs == 1, stride_draw >= n_obs: transposed block by block, with the horizon - 1 extra rows the last
+ * step of a block needs); other strides return PLA_ERR_UNSUPPORTED.  PLA_DEVICE: everything is enqueued on `stream`, the outputs,
+ * first_high and n_replaced (one int64 each) are device pointers, and nothing is allocated once the workspace fits
+ * (pla_engine_set_frozen).  PLA_HOST: the matrix is staged in 1 GiB blocks and the call returns when the results are there.
+ */
+int pla_lfo_ratios(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                   int64_t first, int64_t n_steps, int mem_space, void *stream, double *out, int64_t *n_replaced /* may be NULL */);
+int pla_lfo(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+            int64_t first, int64_t n_steps, int64_t horizon, int method, int64_t tail_count, double k_threshold, int mem_space,
+            void *stream, double *diag /* may be NULL */, double *elpd_i /* may be NULL */, int64_t *first_high /* may be NULL */,
+            int64_t *n_replaced /* may be NULL */);
+
 /* Timing of the dominant kernel, measured with hipEvents on the launch stream.
  * enable != 0 brackets every main-kernel launch with events; pla_engine_kernel_ms returns the
  * accumulated milliseconds and launch count since the last call (it synchronises the events). */

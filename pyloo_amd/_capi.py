@@ -35,7 +35,7 @@ SYMBOLS = (
     "pla_kfold_lme", "pla_kfold_reduce",
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
-    "pla_loo_pit",
+    "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
 )
 
 
@@ -122,6 +122,8 @@ def load_library():
     lib.pla_engine_set_mixis_grid.argtypes = [vp, ci]
     lib.pla_mixis_tile_rows.argtypes = [i64]
     lib.pla_loo_pit.argtypes = [vp, vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, i64, ci, vp, vp, vp, vp, vp]
+    lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
+    lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

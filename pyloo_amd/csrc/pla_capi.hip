@@ -107,6 +107,8 @@ struct pla_engine {
   int mixis_grid = 0;  // pla_engine_set_mixis_grid (0: the library's choice)
   void* d_pit = nullptr;  // LOO-PIT (pla_pit.h): one block of predictive draws, draws fastest (transposed or staged from the host)
   size_t d_pit_bytes = 0;
+  void* d_lfo = nullptr;  // leave-future-out CV (pla_lfo.h): the carry into a block of steps [n_draws], then the carries of its chunks
+  size_t d_lfo_bytes = 0;
   std::string kf_label;  // the routes of the last pla_kfold_lme, for the text pla_kfold_reduce leaves in last_kernels
   int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
   int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
@@ -376,6 +378,7 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_mm) (void)hipFree(e->d_mm);
   if (e->d_mix) (void)hipFree(e->d_mix);
   if (e->d_pit) (void)hipFree(e->d_pit);
+  if (e->d_lfo) (void)hipFree(e->d_lfo);
   for (int i = 0; i < 2; ++i) {
     if (e->h_kf[i]) (void)hipHostFree(e->h_kf[i]);
     if (e->kf_event[i]) (void)hipEventDestroy(e->kf_event[i]);
@@ -2231,6 +2234,219 @@ int pla_loo_pit(pla_engine* eng, const void* in, const void* y_hat, const double
   PLA_HIP(hipStreamSynchronize(s));
   if (n_replaced) *n_replaced = (int64_t)h;
   return PLA_OK;
+}
+
+// ---- leave-future-out CV (csrc/pla_lfo.h) ----------------------------------------------------------------------------------------
+// One block of steps at a time -- whole chunks of the prefix sum, sized like the other staged passes -- on the caller's stream:
+//   1. the log ratios of the block (f64) into the ingest staging d_in: totals, carries (continued from block to block), ratios
+//   2. the weights pass of pla_importance_weights, unchanged, from d_in into d_lw
+//   3. the predict kernel: d_lw against the M future rows of every step, before the next block overwrites either buffer
+// The matrix is read in place when its draws are contiguous on the device; observations-fastest device matrices and host matrices
+// come as blocks of nb + M - 1 rows, draws fastest, in d_pit (transposed on the device / copied).  ratios_out: pla_lfo_ratios (step 1
+// alone, straight into the caller's matrix or through d_in to the host).
+static int lfo_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                    int64_t first, int64_t n_steps, int64_t horizon, int64_t tail_count, double k_threshold, int mem_space, void* stream,
+                    double* ratios_out, double* diag, double* elpd_i, int64_t* first_high, int64_t* n_replaced) {
+  const bool ratios_only = ratios_out != nullptr;
+  const bool host = mem_space == PLA_HOST;
+  const bool in_of = host && host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw);
+  const bool dev_of = obs_fastest_device(mem_space, nullptr, n_obs, n_draws, stride_obs, stride_draw);
+  if (stride_draw != 1 && !in_of && !dev_of)
+    return fail(PLA_ERR_UNSUPPORTED, "the matrix needs unit stride along the draws, or along the observations (stride_draw >= n_obs)");
+  if (stride_draw == 1 && n_obs > 1 && stride_obs < n_draws) return fail(PLA_ERR_ARG, "stride_obs is smaller than n_draws");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int S = (int)n_draws;
+  const int64_t C = pla::lfo_chunk_rows();
+  const int64_t extra = ratios_only ? 0 : horizon - 1;  // rows a block needs beyond one per step
+  const bool staged = host || dev_of;
+
+  // steps per block: the staging's size in f64 ratios, whole chunks
+  int64_t rows = staged_chunk_rows(mem_space, true, n_steps, n_draws, sizeof(double));
+  const bool split = !ratios_only && n_draws > 4096 && tail_count <= 448;  // (the split weights route of long rows: pla_importance_weights)
+  if (split && rows > ((int64_t)1 << 17)) rows = (int64_t)1 << 17;
+  if (rows < n_steps) rows = rows / C * C < C ? C : rows / C * C;
+  if (rows > n_steps) rows = n_steps;
+  const int64_t chunks = (rows + C - 1) / C;
+  const size_t block_bytes = (size_t)rows * (size_t)n_draws * sizeof(double);
+  int rc = grow(&eng->d_lfo, &eng->d_lfo_bytes, (size_t)(chunks + 1) * (size_t)n_draws * sizeof(double));
+  if (rc) return rc;
+  double* run = (double*)eng->d_lfo;
+  double* carry = run + n_draws;
+  if (!ratios_only || host) {
+    rc = grow(&eng->d_in, &eng->d_in_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  if (staged) {
+    const size_t stage_bytes = (size_t)(rows + extra) * (size_t)n_draws * esz;
+    rc = grow(&eng->d_pit, &eng->d_pit_bytes, stage_bytes);
+    if (rc) return rc;
+    if (in_of) {
+      rc = grow(&eng->d_slab, &eng->d_slab_bytes, stage_bytes);
+      if (rc) return rc;
+    }
+  }
+  pla::RowsParams p{};
+  if (!ratios_only) {
+    p.n_draws = S;
+    p.method = PLA_PSIS;
+    p.tail_count = (int)tail_count;
+    p.tail_cap = pow2_at_least(p.tail_count);
+    p.scale_value = 1.0;
+    p.counters = eng->counters;
+    p.stride_obs = n_draws;
+    p.stride_draw = 1;
+    PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));
+    rc = grow(&eng->d_slow, &eng->d_slow_bytes, (size_t)rows * sizeof(unsigned));
+    if (rc) return rc;
+    p.slow_list = (unsigned*)eng->d_slow;
+    rc = ensure_l1_table(eng, tail_count, s, &p.l1_table);
+    if (rc) return rc;
+    if (split) {
+      const int stride = (int)((tail_count + 63) & ~(int64_t)63);
+      rc = grow(&eng->d_ws, &eng->d_ws_bytes, (size_t)rows * (size_t)(stride + 8) * sizeof(double));
+      if (rc && rc != PLA_ERR_NOMEM) return rc;
+      if (!rc) {  // (no room: the fused weights kernel, which needs none)
+        p.ws_y = (double*)eng->d_ws;
+        p.ws_s = p.ws_y + (size_t)rows * stride;
+        p.ws_stride = stride;
+        p.ws_sstride = 8;
+        p.lw_split = true;
+      }
+    }
+    rc = grow(&eng->d_lw, &eng->d_lw_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  // outputs: the caller's device arrays, or engine memory (a host call; k when the caller wants first_high without it)
+  double *d_diag = diag, *d_elpd = elpd_i;
+  unsigned long long* d_count = (unsigned long long*)n_replaced;
+  long long* d_high = (long long*)first_high;
+  if (host) {
+    d_count = eng->counters + pla::kCounterLfoReplaced;
+    d_high = (long long*)(eng->counters + pla::kCounterLfoFirstHigh);
+  }
+  if (!ratios_only && (host || (!diag && first_high))) {
+    size_t have_b = eng->d_pw_elems * sizeof(double);
+    rc = grow((void**)&eng->d_pw, &have_b, (size_t)(2 * n_steps + PLA_AGG_COUNT) * sizeof(double));
+    eng->d_pw_elems = have_b / sizeof(double);
+    if (rc) return rc;
+    d_diag = eng->d_pw;
+    if (host) d_elpd = eng->d_pw + n_steps;
+  }
+  if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  PLA_HIP(hipMemsetAsync(run, 0, (size_t)n_draws * sizeof(double), s));
+
+  std::string label;
+  char route[160];
+  const size_t row_bytes = (size_t)n_draws * esz;
+  for (int64_t j0 = 0; j0 < n_steps; j0 += rows) {
+    const int64_t nb = n_steps - j0 < rows ? n_steps - j0 : rows;
+    const bool last = j0 + nb == n_steps;
+    const int64_t r0 = first + j0;  // the row of the block's first step
+    int64_t n_stage = nb + extra;   // rows of the matrix the block touches (the ratios of the last block stop one row short)
+    if (n_stage > n_obs - r0) n_stage = n_obs - r0;
+    const void* blk = (const char*)ll + (size_t)r0 * (size_t)stride_obs * esz;
+    int64_t blk_so = stride_obs;
+    if (staged && n_stage > 0) {
+      if (dev_of) {
+        PLA_HIP(pla::launch_transpose_rows(ll, dtype, stride_draw, r0, n_stage, S, eng->d_pit, s));
+      } else if (in_of) {  // the (n_draws, n_stage) slab as it lies, turned on the device
+        PLA_HIP(hipMemcpy2DAsync(eng->d_slab, (size_t)n_stage * esz, (const char*)ll + (size_t)r0 * esz, (size_t)stride_draw * esz,
+                                 (size_t)n_stage * esz, (size_t)n_draws, hipMemcpyHostToDevice, s));
+        PLA_HIP(pla::launch_transpose_rows(eng->d_slab, dtype, n_stage, 0, n_stage, S, eng->d_pit, s));
+      } else {
+        PLA_HIP(hipMemcpy2DAsync(eng->d_pit, row_bytes, blk, (size_t)stride_obs * esz, row_bytes, (size_t)n_stage, hipMemcpyHostToDevice, s));
+      }
+    }
+    if (staged) {
+      blk = eng->d_pit;
+      blk_so = n_draws;
+    }
+    double* lr = (ratios_only && !host) ? ratios_out + (size_t)j0 * (size_t)n_draws : (double*)eng->d_in;
+    const char* scan = "";
+    PLA_HIP(pla::launch_lfo_ratios(blk, dtype, blk_so, S, nb, last ? nb - 1 : nb, last, carry, run, lr, ratios_only ? d_count : nullptr, s,
+                                   &scan));
+    if (ratios_only) {
+      if (j0 == 0) label = std::string(scan) + " + lfo_carry_kernel";
+      if (host) {
+        PLA_HIP(hipMemcpyAsync(ratios_out + (size_t)j0 * (size_t)n_draws, lr, (size_t)nb * (size_t)n_draws * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+        PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+      }
+      continue;
+    }
+    p.in = lr;
+    p.n_obs = nb;
+    p.diag = d_diag ? d_diag + j0 : nullptr;
+    p.lw_out = eng->d_lw;
+    {
+      TimedLaunch t(eng, s);
+      PLA_HIP(pla::launch_rows(p, PLA_F64, true, s));
+    }
+    PLA_HIP(pla::launch_lfo_predict((const double*)eng->d_lw, blk, dtype, blk_so, nb, S, (int)horizon, j0 == 0, d_diag ? d_diag + j0 : nullptr,
+                                    d_elpd ? d_elpd + j0 : nullptr, d_count, s, route, (int)sizeof(route)));
+    if (j0 == 0)
+      label = std::string(dev_of ? "transpose_rows_kernel -> " : "") + scan + " + lfo_carry_kernel -> " + pla::last_rows_kernels() + " -> " +
+              route + (host ? " (matrix staged in blocks)" : " per block of steps");
+    if (host) PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+  }
+  eng->last_kernels = label;
+  if (!ratios_only && d_high) PLA_HIP(pla::launch_lfo_first_high(d_diag, n_steps, k_threshold, d_high, s));
+  if (!host) return PLA_OK;
+  if (diag) PLA_HIP(hipMemcpyAsync(diag, d_diag, (size_t)n_steps * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (elpd_i) PLA_HIP(hipMemcpyAsync(elpd_i, d_elpd, (size_t)n_steps * sizeof(double), hipMemcpyDeviceToHost, s));
+  unsigned long long h_count = 0;
+  long long h_high = n_steps;
+  PLA_HIP(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, s));
+  if (!ratios_only) PLA_HIP(hipMemcpyAsync(&h_high, d_high, sizeof(h_high), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h_count;
+  if (first_high) *first_high = (int64_t)h_high;
+  return PLA_OK;
+}
+
+static int lfo_check(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                     int64_t first, int64_t n_steps, int64_t last_row_margin, int mem_space) {
+  // (the engine last: an argument error is reported as such with or without one)
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (n_obs < 1) return fail(PLA_ERR_ARG, "n_obs < 1");
+  if (n_draws < 2 || n_draws > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_draws out of range (at least 2)");
+  if (stride_obs <= 0 || stride_draw <= 0) return fail(PLA_ERR_ARG, "strides must be positive");
+  if (!ll) return fail(PLA_ERR_ARG, "ll is NULL");
+  if (first < 0 || first > n_obs) return fail(PLA_ERR_ARG, "first out of range (0 .. n_obs)");
+  if (n_steps < 1 || n_steps > n_obs - first - last_row_margin + 1)
+    return fail(PLA_ERR_ARG, "n_steps out of range: 1 .. %lld for n_obs %lld, first %lld", (long long)(n_obs - first - last_row_margin + 1),
+                (long long)n_obs, (long long)first);
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  return PLA_OK;
+}
+
+int pla_lfo_ratios(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                   int64_t first, int64_t n_steps, int mem_space, void* stream, double* out, int64_t* n_replaced) {
+  // (step j needs rows first .. first + j - 1: n_steps <= n_obs - first + 1)
+  if (!out) return fail(PLA_ERR_ARG, "out is NULL");
+  const int rc = lfo_check(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, first, n_steps, 0, mem_space);
+  if (rc) return rc;
+  return lfo_impl(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, first, n_steps, 1, 0, 0.0, mem_space, stream, out, nullptr, nullptr,
+                  nullptr, n_replaced);
+}
+
+int pla_lfo(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw, int64_t first,
+            int64_t n_steps, int64_t horizon, int method, int64_t tail_count, double k_threshold, int mem_space, void* stream, double* diag,
+            double* elpd_i, int64_t* first_high, int64_t* n_replaced) {
+  if (method != PLA_PSIS && method != PLA_SIS && method != PLA_TIS) return fail(PLA_ERR_ARG, "bad method");
+  if (method != PLA_PSIS) return fail(PLA_ERR_UNSUPPORTED, "method: leave-future-out CV takes PLA_PSIS only");
+  if (horizon < 1) return fail(PLA_ERR_ARG, "horizon < 1");
+  if (k_threshold != k_threshold) return fail(PLA_ERR_ARG, "k_threshold is NaN");
+  int rc = lfo_check(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, first, n_steps, horizon, mem_space);
+  if (rc) return rc;
+  rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, mem_space);
+  if (rc) return rc;
+  return lfo_impl(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, first, n_steps, horizon, tail_count, k_threshold, mem_space, stream,
+                  nullptr, diag, elpd_i, first_high, n_replaced);
 }
 
 static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, const int64_t* row_index, int64_t n_obs,

@@ -216,6 +216,20 @@ hipError_t launch_pit_prepare(const void* in, int dtype, int64_t stride_obs, int
 hipError_t launch_pit(const void* lw, const void* yh, const double* y, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs,
                       int64_t lw_stride_draw, int64_t yh_stride_obs, int64_t yh_stride_draw, double* pit_le, double* pit_lt,
                       hipStream_t stream, char* route, int cap);
+// leave-future-out CV (pla_lfo.h).  launch_lfo_ratios: the log ratios of one block of n_rows steps -- whole chunks of
+// lfo_chunk_rows() steps unless it is the last block -- as a contiguous (n_rows, n_draws) f64 matrix; `in` is the row of the block's
+// first step (draws contiguous), rows j < n_load of the block are read (NaN -> -1e10, counted in `replaced`, may be null); carry:
+// ceil(n_rows / chunk) * n_draws doubles of workspace; run [n_draws]: the carry into the block (zero before the first), left as the
+// carry into the next.  launch_lfo_predict: elpd and (step 0 of a pass) k = 0 of a block of steps from its log weights and the
+// matrix read in place (draws contiguous, any row stride).  launch_lfo_first_high: *out = the smallest j >= 1 with diag[j] > threshold, else n_steps.
+int lfo_chunk_rows();
+hipError_t launch_lfo_ratios(const void* in, int dtype, int64_t stride_obs, int n_draws, int64_t n_rows, int64_t n_load, bool last_block,
+                             double* carry, double* run, double* out, unsigned long long* replaced, hipStream_t stream,
+                             const char** route);
+hipError_t launch_lfo_predict(const double* lw, const void* ll, int dtype, int64_t ll_stride_obs, int64_t n_steps,
+                              int n_draws, int horizon, bool pass_start, double* diag, double* elpd, unsigned long long* replaced,
+                              hipStream_t stream, char* route, int cap);
+hipError_t launch_lfo_first_high(const double* diag, int64_t n_steps, double threshold, long long* out, hipStream_t stream);
 // moment matching (pla_mm.h): batched moments, affine transform and ratio assembly, f64, device memory
 constexpr int kMmMaxCovDim = 64;  // D with matrices (moments with cov, transform with a matrix)
 constexpr int kMmMaxDim = 1024;   // D without

@@ -3,7 +3,7 @@
 Mirrors the LOO part of the reference container (pyloo/elpd.py:100-498): same index keys,
 same properties, same printed report (README.md:76-84 of the reference; the LOGO report of elpd.py:165-220), including the Pareto-k
 table with bins ``(-inf, good_k], (good_k, 1], (1, inf)`` (elpd.py:300-330), the k-fold report (elpd.py:64-72, 130-163) and the
-report of a Mix-IS-LOO result, which has no ``p_loo`` (elpd.py:364-374).  The
+report of a Mix-IS-LOO result, which has no ``p_loo`` (elpd.py:364-374); the leave-future-out report is this package's own.  The
 sub-sampling and non-factorised report variants are out of scope.
 """
 
@@ -51,6 +51,14 @@ with {n_points} observations.{stratify_msg}
 elpd_kfold   {elpd:<8.2f}    {se:<.2f}
 p_kfold       {p_kfold:<8.2f}    {p_kfold_se:<.2f}
 kfoldic      {kfoldic:<8.2f}    {kfoldic_se:<.2f}
+"""
+
+_LFO_REPORT = """
+Computed from {n_samples} posterior samples using {M}-step-ahead leave-future-out cross-validation
+with {n_points} steps (L = {L}), {n_refits} refits at k > {thr:.2f}.
+
+         Estimate       SE
+elpd_lfo   {elpd:<8.2f}    {se:<.2f}
 """
 
 _K_TABLE = """
@@ -105,6 +113,8 @@ class ELPDData(pd.Series):
                                         kfoldic=-2 * self["elpd_kfold"], kfoldic_se=2 * self["se"],
                                         stratify_msg=" Using stratified k-fold cross-validation" if self.stratified else "")
             return text + (_WARNED if self.warning else "")
+        if kind == "lfo":
+            return self._lfo_report()
         if kind != "loo":
             raise ValueError("Invalid ELPDData object")
         tail = ""
@@ -147,6 +157,26 @@ class ELPDData(pd.Series):
             else:
                 pct = counts / counts.sum() * 100
                 text += _K_TABLE.format(gk=gk, c0=int(counts[0]), c1=int(counts[1]), c2=int(counts[2]), p0=pct[0], p1=pct[1], p2=pct[2])
+        return text
+
+    def _lfo_report(self):
+        """Leave-future-out CV (loo_lfo.py), in the style of the k-fold report: the header, the warning line, then the Pareto k of
+        the steps against the refit threshold when k is there (steps without one -- NaN -- are left out)."""
+        text = _LFO_REPORT.format(n_samples=self.n_samples, M=self["M"], n_points=self.n_data_points, L=self["L"],
+                                  n_refits=self["n_refits"], thr=self["k_threshold"], elpd=self["elpd_lfo"], se=self["se"])
+        if self.warning:
+            text += _WARNED
+        if "pareto_k" in self:
+            gk = self["k_threshold"]
+            kv = _k_values(self["pareto_k"])
+            kv = kv[~np.isnan(kv)]
+            if np.isfinite(gk) and gk < 1 and kv.size:
+                counts = np.histogram(kv, bins=np.asarray([-np.inf, gk, 1, np.inf]))[0]
+                if counts[1] == 0 and counts[2] == 0:
+                    text += _ALL_GOOD.format(gk=gk)
+                else:
+                    pct = counts / counts.sum() * 100
+                    text += _K_TABLE.format(gk=gk, c0=int(counts[0]), c1=int(counts[1]), c2=int(counts[2]), p0=pct[0], p1=pct[1], p2=pct[2])
         return text
 
     def __repr__(self):

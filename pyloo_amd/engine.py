@@ -834,6 +834,72 @@ class Engine:
                                     int(tail_count), PLA_HOST, None, p(pit_le), p(pit_lt), p(diag), C.byref(nrep)))
         return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": int(nrep.value)}
 
+    # ------------------------------------------------------------------ leave-future-out CV
+    def _lfo_input(self, ll):
+        """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None).  A CUDA tensor with the draws or
+        the observations contiguous is read in place (any other strides: a contiguous copy); a host array in the same two layouts."""
+        if _is_torch_tensor(ll):
+            import torch
+
+            if ll.dim() != 2 or not ll.is_cuda:
+                raise ValueError("expected a 2-D CUDA tensor")
+            if ll.dtype not in (torch.float64, torch.float32):
+                raise TypeError(f"unsupported dtype {ll.dtype}")
+            t = self._library_layout(ll)
+            if t.shape[1] > 1 and t.stride(1) == 1 and t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                t = t.contiguous()  # (rows that overlap: an expanded tensor)
+            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            so = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+            return t, t.shape[0], t.shape[1], so, t.stride(1), code, PLA_DEVICE, self._stream(), t.device
+        a = self._as_2d_host(ll, allow_obs_fastest=True)
+        so, sd = self._host_strides(a)
+        return a, a.shape[0], a.shape[1], so, sd, dtype_code(a.dtype), PLA_HOST, None, None
+
+    def lfo_ratios(self, ll, first, n_steps):
+        """Log ratios of leave-future-out CV (``pla_lfo_ratios``): ``dict(ratios, n_replaced)`` with ``ratios[j, s]`` the sum of rows
+        ``first .. first + j - 1`` of the (n_obs, n_draws) log-likelihood ``ll``, always float64, in the summation order
+        include/pyloo_amd.h documents.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out, nothing synchronised."""
+        a, n, s, so, sd, code, space, stream, device = self._lfo_input(ll)
+        first, n_steps = int(first), int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        if device is None:
+            out = np.empty((n_steps, s))
+        else:
+            import torch
+
+            out = torch.empty((n_steps, s), dtype=torch.float64, device=device)
+        p = self._mixis_ptr
+        if device is None:
+            nrep = C.c_int64(0)
+            check(self._lib.pla_lfo_ratios(self._h, p(a), code, n, s, so, sd, first, n_steps, space, stream, p(out), C.byref(nrep)))
+            return {"ratios": out, "n_replaced": int(nrep.value)}
+        nrep = self._mixis_new(1, device, "int64")
+        check(self._lib.pla_lfo_ratios(self._h, p(a), code, n, s, so, sd, first, n_steps, space, stream, p(out), p(nrep)))
+        return {"ratios": out, "n_replaced": nrep}
+
+    def lfo(self, ll, first, n_steps, horizon=1, tail_count=0, k_threshold=0.7, method="psis"):
+        """One pass of PSIS leave-future-out CV over the steps ``first .. first + n_steps - 1`` of one fit (``pla_lfo``):
+        ``dict(diag, elpd_i, first_high, n_replaced)``.  ``diag[0] = 0`` (the fit's own step is exact); ``first_high`` is the
+        smallest ``j >= 1`` with ``diag[j] > k_threshold``, else ``n_steps``.  NumPy in -> NumPy out (and two ints); CUDA tensor in
+        -> CUDA tensors out (``first_high`` and ``n_replaced`` one int64 each), nothing synchronised."""
+        mcode = METHOD_CODES[method]
+        a, n, s, so, sd, code, space, stream, device = self._lfo_input(ll)
+        first, n_steps, horizon = int(first), int(n_steps), int(horizon)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        diag, elpd = self._mixis_new(n_steps, device), self._mixis_new(n_steps, device)
+        p = self._mixis_ptr
+        if device is None:
+            high, nrep = C.c_int64(0), C.c_int64(0)
+            check(self._lib.pla_lfo(self._h, p(a), code, n, s, so, sd, first, n_steps, horizon, mcode, int(tail_count), float(k_threshold),
+                                    space, stream, p(diag), p(elpd), C.byref(high), C.byref(nrep)))
+            return {"diag": diag, "elpd_i": elpd, "first_high": int(high.value), "n_replaced": int(nrep.value)}
+        high, nrep = self._mixis_new(1, device, "int64"), self._mixis_new(1, device, "int64")
+        check(self._lib.pla_lfo(self._h, p(a), code, n, s, so, sd, first, n_steps, horizon, mcode, int(tail_count), float(k_threshold),
+                                space, stream, p(diag), p(elpd), p(high), p(nrep)))
+        return {"diag": diag, "elpd_i": elpd, "first_high": high, "n_replaced": nrep}
+
     def e_loo_quantiles(self, x, log_weights, probs):
         """(n_obs, n_draws) draws + log-weights, quantile levels -> (n_obs, n_probs) weighted quantiles (``pla_e_loo_quantiles``:
         e_loo.py:468-515, 534-554)."""
