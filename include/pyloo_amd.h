@@ -571,6 +571,40 @@ int pla_lfo(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n
             void *stream, double *diag /* may be NULL */, double *elpd_i /* may be NULL */, int64_t *first_high /* may be NULL */,
             int64_t *n_replaced /* may be NULL */);
 
+/*
+ * Relative MCMC efficiency of every row of a matrix (csrc/pla_ess.h): r_eff[i] = ESS / n_draws' of the mean of row i, Stan's
+ * estimator for the mean (Vehtari et al. 2021; Geyer's initial positive and monotone sequences) without rank normalisation --
+ * relative_eff() of R-loo, the `reff` every PSIS entry point here takes (pass its mean).  The reference has no counterpart: its
+ * loo.py:204-216 asks ArviZ for the ESS of the posterior.
+ *   x        (n_obs, n_draws), PLA_F64 / PLA_F32, const.  A row is n_chains chains of n_draws / n_chains draws, chain major.
+ *   flags    PLA_ESS_LOG    the rows are log-likelihoods: exp(x - row maximum) is analysed (the estimate is scale-invariant); else x.
+ *            PLA_ESS_SPLIT  every chain of n0 draws becomes two, its first and its last n0 / 2 draws (the middle one of an odd chain
+ *                           is dropped): ArviZ / posterior.  Without it: R-loo.
+ *            PLA_ESS_CAP    results above 1 (antithetic chains) are returned as 1, as R-loo does.
+ * With C chains of n draws after the split, d[c][i] the draws minus their chain mean m_c, all in f64:
+ *     A(t) = sum_c sum_{i < n - t} d[c][i] d[c][i + t] / (C n)     W = A(0) n / (n - 1)     V = A(0) + var(m_c, ddof 1) (0 for C = 1)
+ *     rho(t) = 1 - (W - A(t)) / V;  pairs (rho(t), rho(t + 1)), t = 2, 4, ..., are taken while t < n - 1 and the previous pair's sum is
+ *     positive; a pair with a negative sum counts as zero; a pair above its predecessor counts as its predecessor;
+ *     tau = -1 + 2 sum of the pairs (the first is 1 + rho(1)) + max(last rho(even), 0), at least 1 / log10(C n);  r_eff = 1 / tau.
+ * The order of every sum is fixed (csrc/pla_ess.h), so the bits do not depend on the grid, the layout or the memory space.
+ * Invalid rows -- a NaN or +inf entry (-inf too without PLA_ESS_LOG), a constant row (every entry -inf included), a variance that is
+ * not positive and finite -- give NaN and are counted in *n_invalid (may be NULL).  Single -inf entries of a log row are likelihood 0.
+ * Needs n_chains >= 1 dividing n_draws and at least 4 draws per chain after the split (PLA_ERR_ARG otherwise).  Rows of up to
+ * pla_ess_lds_max_draws() analysed draws are read once and kept on chip; longer ones go through engine workspace.
+ * Layouts, in either memory space: draws fastest (stride_draw == 1, any stride_obs >= n_draws: read in place on the device), or
+ * observations fastest (stride_obs == 1, stride_draw >= n_obs: transposed block by block into staging); other strides return
+ * PLA_ERR_UNSUPPORTED.  PLA_DEVICE: everything is enqueued on `stream`, r_eff [n_obs] and n_invalid (one int64) are device pointers
+ * and nothing is allocated once the workspace fits.  PLA_HOST: the matrix is staged in 1 GiB blocks.
+ * pla_engine_set_ess_grid caps the workgroups of the pass (0: the library's choice) -- a test hook: the results do not depend on it.
+ */
+#define PLA_ESS_LOG 1
+#define PLA_ESS_SPLIT 2
+#define PLA_ESS_CAP 4
+int pla_relative_eff(pla_engine *eng, const void *x, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                     int64_t n_chains, int flags, int mem_space, void *stream, double *r_eff, int64_t *n_invalid /* may be NULL */);
+int pla_engine_set_ess_grid(pla_engine *eng, int max_workgroups);
+int pla_ess_lds_max_draws(void);
+
 /* Timing of the dominant kernel, measured with hipEvents on the launch stream.
  * enable != 0 brackets every main-kernel launch with events; pla_engine_kernel_ms returns the
  * accumulated milliseconds and launch count since the last call (it synchronises the events). */

@@ -15,6 +15,7 @@ AGG_COUNT = 8
 ABI_VERSION = 7
 PLA_MVN_NORMAL, PLA_MVN_STUDENT_T = 0, 1
 PLA_PIT_LOGLIK, PLA_PIT_LOG_WEIGHTS = 0, 1  # input_kind of pla_loo_pit
+PLA_ESS_LOG, PLA_ESS_SPLIT, PLA_ESS_CAP = 1, 2, 4  # flags of pla_relative_eff
 PLA_NONFACTOR_MAX_OBS = 1024
 # status word of a draw of pla_nonfactor_loglik
 NF_GENERAL, NF_SINGULAR, NF_NONFINITE, NF_DF_NONPOS, NF_BETA_NONFINITE, NF_CLAMPED = 1, 2, 4, 8, 16, 32
@@ -36,6 +37,7 @@ SYMBOLS = (
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
+    "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
 
 
@@ -124,6 +126,9 @@ def load_library():
     lib.pla_loo_pit.argtypes = [vp, vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, i64, ci, vp, vp, vp, vp, vp]
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
+    lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]
+    lib.pla_engine_set_ess_grid.argtypes = [vp, ci]
+    lib.pla_ess_lds_max_draws.argtypes = []
     for name in SYMBOLS:
         getattr(lib, name)  # AttributeError if the header and the library disagree
         if name != "pla_last_error":

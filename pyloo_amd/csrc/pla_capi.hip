@@ -109,6 +109,9 @@ struct pla_engine {
   size_t d_pit_bytes = 0;
   void* d_lfo = nullptr;  // leave-future-out CV (pla_lfo.h): the carry into a block of steps [n_draws], then the carries of its chunks
   size_t d_lfo_bytes = 0;
+  void* d_ess = nullptr;  // relative efficiency (pla_ess.h): a slot of centred draws per workgroup of the long-row route
+  size_t d_ess_bytes = 0;
+  int ess_grid = 0;  // pla_engine_set_ess_grid (0: the library's choice)
   std::string kf_label;  // the routes of the last pla_kfold_lme, for the text pla_kfold_reduce leaves in last_kernels
   int nonfactor_route = 0;  // pla_engine_set_nonfactor_route
   int nonfactor_grid = 0;   // pla_engine_set_nonfactor_grid (0: the library's choice)
@@ -379,6 +382,7 @@ int pla_engine_destroy(pla_engine* e) {
   if (e->d_mix) (void)hipFree(e->d_mix);
   if (e->d_pit) (void)hipFree(e->d_pit);
   if (e->d_lfo) (void)hipFree(e->d_lfo);
+  if (e->d_ess) (void)hipFree(e->d_ess);
   for (int i = 0; i < 2; ++i) {
     if (e->h_kf[i]) (void)hipHostFree(e->h_kf[i]);
     if (e->kf_event[i]) (void)hipEventDestroy(e->kf_event[i]);
@@ -2447,6 +2451,109 @@ int pla_lfo(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n
   if (rc) return rc;
   return lfo_impl(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, first, n_steps, horizon, tail_count, k_threshold, mem_space, stream,
                   nullptr, diag, elpd_i, first_high, n_replaced);
+}
+
+// ---- relative MCMC efficiency (csrc/pla_ess.h) -----------------------------------------------------------------------------------
+// One kernel per block of observations on the caller's stream.  Draws-fastest device matrices are read in place in one launch;
+// observations-fastest ones are transposed block by block into the ingest staging d_in, host matrices are uploaded into it (and
+// transposed there when their observations are fastest) -- the same kernel then runs on the staged block.
+int pla_engine_set_ess_grid(pla_engine* eng, int max_workgroups) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (max_workgroups < 0) return fail(PLA_ERR_ARG, "max_workgroups < 0");
+  EngineCall call(eng);
+  eng->ess_grid = max_workgroups;
+  return PLA_OK;
+}
+
+int pla_ess_lds_max_draws(void) { return pla::ess_lds_max_draws(); }
+
+int pla_relative_eff(pla_engine* eng, const void* x, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                     int64_t n_chains, int flags, int mem_space, void* stream, double* r_eff, int64_t* n_invalid) {
+  // (the engine last: an argument error is reported as such with or without one)
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (n_obs < 1) return fail(PLA_ERR_ARG, "n_obs < 1");
+  if (n_draws < 1 || n_draws > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_draws out of range");
+  if (stride_obs <= 0 || stride_draw <= 0) return fail(PLA_ERR_ARG, "strides must be positive");
+  if (flags & ~(PLA_ESS_LOG | PLA_ESS_SPLIT | PLA_ESS_CAP)) return fail(PLA_ERR_ARG, "unknown bits in flags");
+  if (n_chains < 1 || n_draws % n_chains != 0)
+    return fail(PLA_ERR_ARG, "n_chains = %lld does not divide n_draws = %lld", (long long)n_chains, (long long)n_draws);
+  const bool split = (flags & PLA_ESS_SPLIT) != 0;
+  const int64_t n_src = n_draws / n_chains;
+  const int64_t n = split ? n_src / 2 : n_src;
+  if (n < 4) return fail(PLA_ERR_ARG, "a chain has %lld draws%s: at least 4 are needed", (long long)n, split ? " after the split" : "");
+  if (!x) return fail(PLA_ERR_ARG, "x is NULL");
+  if (!r_eff) return fail(PLA_ERR_ARG, "r_eff is NULL");
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  const bool host = mem_space == PLA_HOST;
+  const bool in_of = host && host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw);
+  const bool dev_of = obs_fastest_device(mem_space, nullptr, n_obs, n_draws, stride_obs, stride_draw);
+  if (stride_draw != 1 && !in_of && !dev_of)
+    return fail(PLA_ERR_UNSUPPORTED, "the matrix needs unit stride along the draws, or along the observations (stride_draw >= n_obs)");
+  if (stride_draw == 1 && n_obs > 1 && stride_obs < n_draws) return fail(PLA_ERR_ARG, "stride_obs is smaller than n_draws");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const size_t row_bytes = (size_t)n_draws * esz;
+  const bool staged = host || dev_of;
+  const int64_t rows = staged ? staged_chunk_rows(mem_space, true, n_obs, n_draws, esz) : n_obs;
+  const int64_t analysed = (split ? 2 * n_chains : n_chains) * n;
+  int rc;
+  double* ws = nullptr;
+  if (analysed > pla::ess_lds_max_draws()) {
+    const int64_t slots = pla::ess_grid_for(rows, analysed, eng->ess_grid);
+    rc = grow(&eng->d_ess, &eng->d_ess_bytes, (size_t)slots * (size_t)analysed * sizeof(double));
+    if (rc) return rc;
+    ws = (double*)eng->d_ess;
+  }
+  if (staged) {
+    rc = grow(&eng->d_in, &eng->d_in_bytes, (size_t)rows * row_bytes);
+    if (rc) return rc;
+  }
+  double* d_out = r_eff;
+  unsigned long long* d_count = (unsigned long long*)n_invalid;
+  if (host) {
+    size_t have_b = eng->d_pw_elems * sizeof(double);
+    rc = grow((void**)&eng->d_pw, &have_b, (size_t)(n_obs + PLA_AGG_COUNT) * sizeof(double));
+    eng->d_pw_elems = have_b / sizeof(double);
+    if (rc) return rc;
+    d_out = eng->d_pw;
+    d_count = eng->counters + pla::kCounterEssInvalid;
+  }
+  if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  char route[96];
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+    const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+    const void* blk = x;
+    int64_t blk_so = stride_obs;
+    if (host) {
+      rc = stage_rows(eng, x, nullptr, r0, nr, stride_obs, esz, row_bytes, s, stride_draw, dtype, rows);
+      if (rc) return rc;
+    } else if (dev_of) {
+      PLA_HIP(pla::launch_transpose_rows(x, dtype, stride_draw, r0, nr, (int)n_draws, eng->d_in, s));
+    }
+    if (staged) {
+      blk = eng->d_in;
+      blk_so = n_draws;
+    }
+    {
+      TimedLaunch t(eng, s);
+      PLA_HIP(pla::launch_ess(blk, dtype, blk_so, nr, (int)n_chains, (int)n_src, split ? 1 : 0, (flags & PLA_ESS_LOG) ? 1 : 0,
+                              (flags & PLA_ESS_CAP) ? 1 : 0, ws, eng->ess_grid, d_out + r0, d_count, s, route, (int)sizeof(route)));
+    }
+    if (r0 == 0)
+      eng->last_kernels = std::string(dev_of || in_of ? "transpose_rows_kernel -> " : "") + route +
+                          (host ? " (matrix staged in blocks)" : dev_of ? " per block of observations" : "");
+    if (host) PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next block
+  }
+  if (!host) return PLA_OK;
+  unsigned long long h_count = 0;
+  PLA_HIP(hipMemcpyAsync(r_eff, d_out, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_invalid) *n_invalid = (int64_t)h_count;
+  return PLA_OK;
 }
 
 static int waic_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_src, const int64_t* row_index, int64_t n_obs,

@@ -230,6 +230,14 @@ hipError_t launch_lfo_predict(const double* lw, const void* ll, int dtype, int64
                               int n_draws, int horizon, bool pass_start, double* diag, double* elpd, unsigned long long* replaced,
                               hipStream_t stream, char* route, int cap);
 hipError_t launch_lfo_first_high(const double* diag, int64_t n_steps, double threshold, long long* out, hipStream_t stream);
+// relative MCMC efficiency (pla_ess.h): r_eff of n_rows rows (draws contiguous, any row stride) of n_src_chains chains of n_src draws,
+// chain major.  ws: ess_grid_for(...) slots of the analysed draws in doubles when they exceed ess_lds_max_draws(), else unused;
+// grid_cap: 0 or a cap on the workgroups; invalid: device counter of the NaN results (may be null, never zeroed here).
+int ess_lds_max_draws();
+int64_t ess_grid_for(int64_t n_rows, int64_t analysed, int cap);
+hipError_t launch_ess(const void* in, int dtype, int64_t stride_obs, int64_t n_rows, int n_src_chains, int n_src, int split, int log_mode,
+                      int cap_one, double* ws, int grid_cap, double* out, unsigned long long* invalid, hipStream_t stream, char* route,
+                      int cap);
 // moment matching (pla_mm.h): batched moments, affine transform and ratio assembly, f64, device memory
 constexpr int kMmMaxCovDim = 64;  // D with matrices (moments with cov, transform with a matrix)
 constexpr int kMmMaxDim = 1024;   // D without

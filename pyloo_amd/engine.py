@@ -900,6 +900,33 @@ class Engine:
                                 space, stream, p(diag), p(elpd), p(high), p(nrep)))
         return {"diag": diag, "elpd_i": elpd, "first_high": high, "n_replaced": nrep}
 
+    # ------------------------------------------------------------------ relative MCMC efficiency
+    def relative_eff(self, x, n_chains=1, log=True, split=False, cap=True):
+        """Relative efficiency of every row of an (n_obs, n_draws) matrix of ``n_chains`` equal chains stacked chain-major
+        (``pla_relative_eff``): ``dict(r_eff, n_invalid)``.  Invalid rows (NaN or +inf entries, constant rows) give NaN and are
+        counted.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out (``n_invalid`` one int64), nothing
+        synchronised."""
+        a, n, s, so, sd, code, space, stream, device = self._lfo_input(x)
+        flags = (_capi.PLA_ESS_LOG if log else 0) | (_capi.PLA_ESS_SPLIT if split else 0) | (_capi.PLA_ESS_CAP if cap else 0)
+        r = self._mixis_new(n, device)
+        p = self._mixis_ptr
+        if device is None:
+            ninv = C.c_int64(0)
+            check(self._lib.pla_relative_eff(self._h, p(a), code, n, s, so, sd, int(n_chains), flags, space, stream, p(r), C.byref(ninv)))
+            return {"r_eff": r, "n_invalid": int(ninv.value)}
+        ninv = self._mixis_new(1, device, "int64")
+        check(self._lib.pla_relative_eff(self._h, p(a), code, n, s, so, sd, int(n_chains), flags, space, stream, p(r), p(ninv)))
+        return {"r_eff": r, "n_invalid": ninv}
+
+    def set_ess_grid(self, max_workgroups):
+        """Cap the workgroups per launch of the relative-efficiency pass (0: the library's choice); the results do not depend on it."""
+        check(self._lib.pla_engine_set_ess_grid(self._h, int(max_workgroups)))
+
+    @staticmethod
+    def ess_lds_max_draws():
+        """Analysed draws per row up to which the relative-efficiency pass keeps the row on chip (``pla_ess_lds_max_draws``)."""
+        return load_library().pla_ess_lds_max_draws()
+
     def e_loo_quantiles(self, x, log_weights, probs):
         """(n_obs, n_draws) draws + log-weights, quantile levels -> (n_obs, n_probs) weighted quantiles (``pla_e_loo_quantiles``:
         e_loo.py:468-515, 534-554)."""
