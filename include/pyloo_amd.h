@@ -534,6 +534,45 @@ int pla_loo_pit(pla_engine *eng, const void *in, const void *y_hat, const double
                 double *diag /* may be NULL; written only for PLA_PIT_LOGLIK */, int64_t *n_replaced /* may be NULL */);
 
 /*
+ * LOO diagnostics per observation (csrc/pla_diag.h): how many effective draws stand behind loo_i and what its Monte Carlo error
+ * is.  With ll row i of the log-likelihood (NaN counted as -1e10, +-inf kept), lw its log weights, m = max_s lw_s,
+ * e_s = exp(lw_s - m) and w_s = e_s / sum e (a weight of log -inf is 0 and the draw contributes to nothing):
+ *     elpd_i[i]  = LSE_s(lw_s + ll_s) - LSE_s(lw_s)
+ *     ess_w[i]   = (sum e_s)^2 / sum e_s^2                                       (= 1 / sum w_s^2, in [1, n_draws])
+ *     var_log[i] = log1p( sum_s w_s^2 (exp(ll_s - elpd_i) - 1)^2 )
+ * var_log is the variance of the self-normalised importance-sampling estimator on the linear scale (Vehtari et al. 2024, eq. 6)
+ * over its square, moved to the log scale by log-normal moment matching.  With the relative efficiency r_eff of observation i
+ * (pla_relative_eff): n_eff = r_eff ess_w, mcse_elpd_i = sqrt(var_log / r_eff), mcse_elpd_loo = sqrt(sum mcse_elpd_i^2).
+ * All arithmetic is f64 (f32 input is widened on load).  A row whose weights are all NaN or all -inf, a row with a NaN weight or a
+ * NaN ll, and a row whose elpd_i is -inf (every ll -inf) give NaN in the three values.  Rows with k = +inf are computed on their
+ * unsmoothed weights.  No floating-point atomics; the order of each sum is a rule of n_draws and the dtype alone, so the bits do
+ * not depend on the grid, the block size (PLA_INGEST_BLOCK_MB), the memory space, the layout or the load mode.
+ *
+ * pla_loo_diag          ll (n_obs, n_draws) -> the weights of -ll by `method` and tail_count exactly as pla_importance_weights
+ *                       computes them, then the three values; diag receives Pareto k (PLA_PSIS) or the ESS (PLA_SIS / PLA_TIS).
+ *                       One block of rows at a time, as pla_loo_pit: -ll into the ingest staging, the weights pass into a second
+ *                       bounded buffer, the diagnostics kernel on both before the next block overwrites either.  row_index (NULL:
+ *                       every row, n_rows is ignored) selects n_rows rows, repeats allowed; the list lives where the matrix lives:
+ *                       a device list is clamped into [0, n_obs), a host list out of range is PLA_ERR_ARG.  The outputs are
+ *                       compact, one entry per selected row, and each may be NULL; *n_replaced (may be NULL) counts the NaN
+ *                       entries of the selected rows.  Layouts: draws fastest or observations fastest in either memory space (an
+ *                       observations-fastest matrix with a row_index: on the device through a gather that is correct, not fast;
+ *                       on the host PLA_ERR_UNSUPPORTED), other host strides PLA_ERR_UNSUPPORTED.
+ * pla_loo_diag_weights  the kernel alone on caller-supplied log weights of any normalisation (psislw's output, the weights of a
+ *                       moment-matching result) and ll (NaN is not replaced here), two matrices of one dtype with their own
+ *                       strides.  Device pointers are read in place, any positive strides; host matrices need unit draw strides
+ *                       (PLA_ERR_UNSUPPORTED otherwise) and are staged in blocks.
+ * PLA_DEVICE: everything is enqueued on `stream`, the outputs and n_replaced (one int64) are device pointers, and nothing is
+ * allocated once the workspace fits (pla_engine_set_frozen).  PLA_HOST: the call returns when the results are there.
+ */
+int pla_loo_diag(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                 const int64_t *row_index /* NULL: every row */, int64_t n_rows, int method, int64_t tail_count, int mem_space,
+                 void *stream, double *diag, double *elpd_i, double *ess_w, double *var_log, int64_t *n_replaced);
+int pla_loo_diag_weights(pla_engine *eng, const void *lw, const void *ll, int dtype, int64_t n_obs, int64_t n_draws,
+                         int64_t lw_stride_obs, int64_t lw_stride_draw, int64_t ll_stride_obs, int64_t ll_stride_draw,
+                         int mem_space, void *stream, double *elpd_i, double *ess_w, double *var_log);
+
+/*
  * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
  * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
  * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):

@@ -37,6 +37,7 @@ SYMBOLS = (
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
+    "pla_loo_diag", "pla_loo_diag_weights",
     "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
 
@@ -124,6 +125,8 @@ def load_library():
     lib.pla_engine_set_mixis_grid.argtypes = [vp, ci]
     lib.pla_mixis_tile_rows.argtypes = [i64]
     lib.pla_loo_pit.argtypes = [vp, vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, i64, ci, vp, vp, vp, vp, vp]
+    lib.pla_loo_diag.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, i64, ci, vp, vp, vp, vp, vp, vp]
+    lib.pla_loo_diag_weights.argtypes = [vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp]
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]

@@ -40,6 +40,64 @@ def tail_count_for(n_samples, reff):
     return int(np.ceil(min(n_samples / 5.0, 3 * (n_samples / reff) ** 0.5)))
 
 
+def is_reff_vector(reff):
+    """True for a per-observation ``reff`` (an array or tensor with at least one dimension), False for a scalar."""
+    if _is_torch_tensor(reff):
+        return reff.dim() > 0
+    if isinstance(reff, np.ndarray):
+        return reff.ndim > 0
+    return isinstance(reff, (list, tuple)) or (hasattr(reff, "values") and not callable(reff.values) and np.ndim(reff.values) > 0)
+
+
+def check_reff_vector(reff, n_obs):
+    """A per-observation ``reff`` as a flat float64 vector of length ``n_obs`` of its own kind (NumPy array or CUDA tensor).
+    ``ValueError`` for another length and for an entry that is NaN, infinite or not positive, naming the first such index."""
+    if _is_torch_tensor(reff):
+        import torch
+
+        r = reff.detach().reshape(-1).to(torch.float64)
+        bad = ~(torch.isfinite(r) & (r > 0))
+    else:
+        r = np.asarray(getattr(reff, "values", reff), dtype=np.float64).reshape(-1)
+        bad = ~(np.isfinite(r) & (r > 0))
+    if r.shape[0] != n_obs:
+        raise ValueError(f"reff has {r.shape[0]} values for {n_obs} observations")
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0][0]) if not _is_torch_tensor(r) else int(bad.nonzero()[0, 0])
+        raise ValueError(f"reff[{i}] = {float(r[i])}: every entry must be positive and finite (relative_eff gives NaN for rows it "
+                         "cannot analyse: constant rows, rows with NaN or +inf entries)")
+    return r
+
+
+def tail_buckets(reff, n_draws):
+    """Observations grouped by their own tail count: ``(M, buckets)`` with ``M[i] = tail_count_for(n_draws, reff[i])`` (int64, of the
+    kind of ``reff``) and ``buckets`` the list of ``(m, index)`` over the distinct values ``m`` in ascending order, ``index`` the
+    ascending positions that share it.  ``reff`` is a checked vector (:func:`check_reff_vector`): torch ops for a CUDA tensor, NumPy
+    for a host array.  Entries whose ``3 sqrt(n / r)`` lies within rounding of an integer take the scalar expression itself."""
+    n = float(n_draws)
+    if _is_torch_tensor(reff):
+        import torch
+
+        v = 3.0 * torch.sqrt(n / reff)
+        M = torch.ceil(torch.clamp(v, max=n / 5.0)).to(torch.int64)
+        near = ((v - torch.round(v)).abs() <= 1e-9 * v).nonzero().reshape(-1)
+        if near.numel():
+            fix = [tail_count_for(n_draws, float(x)) for x in reff[near].cpu().tolist()]
+            M[near] = torch.as_tensor(fix, dtype=torch.int64, device=M.device)
+        values, inverse, counts = torch.unique(M, return_inverse=True, return_counts=True)
+        order = torch.argsort(inverse, stable=True)
+        parts = torch.split(order, counts.cpu().tolist())
+        return M, [(int(m), idx) for m, idx in zip(values.cpu().tolist(), parts)]
+    v = 3.0 * np.sqrt(n / reff)
+    M = np.ceil(np.minimum(v, n / 5.0)).astype(np.int64)
+    for i in np.nonzero(np.abs(v - np.round(v)) <= 1e-9 * v)[0]:
+        M[i] = tail_count_for(n_draws, float(reff[i]))
+    values, inverse, counts = np.unique(M, return_inverse=True, return_counts=True)
+    order = np.argsort(inverse.reshape(-1), kind="stable")
+    parts = np.split(order, np.cumsum(counts)[:-1])
+    return M, [(int(m), idx) for m, idx in zip(values, parts)]
+
+
 def _run(values, method, reff):
     """values: ndarray or CUDA tensor (..., S) -> (lw same shape/dtype, diag lead-shape float64)."""
     torchy = _is_torch_tensor(values)

@@ -2053,6 +2053,45 @@ int pla_importance_weights(pla_engine* eng, const void* logw, int dtype, int64_t
   return PLA_OK;
 }
 
+// The weights pass of one block of rows for the passes that consume a block's weights before the next block overwrites them
+// (pla_loo_pit, pla_loo_diag), as pla_importance_weights sets it up: every field of `p` but in / n_obs / diag / lw_out, and the
+// workspace for `*rows` rows per block -- the slow list, the quantile table, the weights buffer d_lw and, for long rows, the
+// hand-over buffers of the split weights route, whose inner blocks of 2^17 rows cap *rows.
+static int weights_block_setup(pla_engine* eng, int method, int64_t tail_count, int64_t n_draws, size_t esz, hipStream_t s, int64_t* rows,
+                               pla::RowsParams* p) {
+  p->n_draws = (int)n_draws;
+  p->method = method;
+  p->tail_count = method == PLA_PSIS ? (int)tail_count : 0;
+  p->tail_cap = pow2_at_least(p->tail_count);
+  p->scale_value = 1.0;
+  p->counters = eng->counters;
+  p->stride_obs = n_draws;
+  p->stride_draw = 1;
+  const bool split = method == PLA_PSIS && n_draws > 4096 && tail_count <= 448;
+  if (split && *rows > ((int64_t)1 << 17)) *rows = (int64_t)1 << 17;
+  PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));
+  int rc = grow(&eng->d_slow, &eng->d_slow_bytes, (size_t)*rows * sizeof(unsigned));
+  if (rc) return rc;
+  p->slow_list = (unsigned*)eng->d_slow;
+  if (method == PLA_PSIS) {
+    rc = ensure_l1_table(eng, tail_count, s, &p->l1_table);
+    if (rc) return rc;
+  }
+  if (split) {
+    const int stride = (int)((tail_count + 63) & ~(int64_t)63);
+    rc = grow(&eng->d_ws, &eng->d_ws_bytes, (size_t)*rows * (size_t)(stride + 8) * sizeof(double));
+    if (rc && rc != PLA_ERR_NOMEM) return rc;
+    if (!rc) {  // (no room: the fused weights kernel, which needs none)
+      p->ws_y = (double*)eng->d_ws;
+      p->ws_s = p->ws_y + (size_t)*rows * stride;
+      p->ws_stride = stride;
+      p->ws_sstride = 8;
+      p->lw_split = true;
+    }
+  }
+  return grow(&eng->d_lw, &eng->d_lw_bytes, (size_t)*rows * (size_t)n_draws * esz);
+}
+
 // ---- LOO-PIT (csrc/pla_pit.h) ---------------------------------------------------------------------------------------------------
 int pla_loo_pit(pla_engine* eng, const void* in, const void* y_hat, const double* y, int dtype, int64_t n_obs, int64_t n_draws,
                 int64_t stride_obs, int64_t stride_draw, int64_t yh_stride_obs, int64_t yh_stride_draw, int input_kind, int method,
@@ -2098,46 +2137,15 @@ int pla_loo_pit(pla_engine* eng, const void* in, const void* y_hat, const double
     return PLA_OK;
   }
 
-  // ---- the weights pass of a block, as pla_importance_weights sets it up
+  // ---- the weights pass of a block, as pla_importance_weights sets it up; rows per block: the ingest staging's size on the device,
+  // 1 GiB from the host
   pla::RowsParams p{};
-  p.n_draws = S;
-  p.method = method;
-  p.tail_count = method == PLA_PSIS ? (int)tail_count : 0;
-  p.tail_cap = pow2_at_least(p.tail_count);
-  p.scale_value = 1.0;
-  p.counters = eng->counters;
-  p.stride_obs = n_draws;
-  p.stride_draw = 1;
-  // rows per block: the ingest staging's size on the device, 1 GiB from the host; long rows keep the split weights route and its
-  // 2^17-row inner blocks (pla_importance_weights)
   int64_t rows = staged_chunk_rows(mem_space, true, n_obs, n_draws, esz);
-  const bool split = loglik && method == PLA_PSIS && n_draws > 4096 && tail_count <= 448;
-  if (split && rows > ((int64_t)1 << 17)) rows = (int64_t)1 << 17;
-  const size_t block_bytes = (size_t)rows * (size_t)n_draws * esz;
   if (loglik) {
-    PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));
-    rc = grow(&eng->d_slow, &eng->d_slow_bytes, (size_t)rows * sizeof(unsigned));
-    if (rc) return rc;
-    p.slow_list = (unsigned*)eng->d_slow;
-    if (method == PLA_PSIS) {
-      rc = ensure_l1_table(eng, tail_count, s, &p.l1_table);
-      if (rc) return rc;
-    }
-    if (split) {
-      const int stride = (int)((tail_count + 63) & ~(int64_t)63);
-      rc = grow(&eng->d_ws, &eng->d_ws_bytes, (size_t)rows * (size_t)(stride + 8) * sizeof(double));
-      if (rc && rc != PLA_ERR_NOMEM) return rc;
-      if (!rc) {  // (no room: the fused weights kernel, which needs none)
-        p.ws_y = (double*)eng->d_ws;
-        p.ws_s = p.ws_y + (size_t)rows * stride;
-        p.ws_stride = stride;
-        p.ws_sstride = 8;
-        p.lw_split = true;
-      }
-    }
-    rc = grow(&eng->d_lw, &eng->d_lw_bytes, block_bytes);
+    rc = weights_block_setup(eng, method, tail_count, n_draws, esz, s, &rows, &p);
     if (rc) return rc;
   }
+  const size_t block_bytes = (size_t)rows * (size_t)n_draws * esz;
   if (loglik || host) {
     rc = grow(&eng->d_in, &eng->d_in_bytes, block_bytes);
     if (rc) return rc;
@@ -2237,6 +2245,177 @@ int pla_loo_pit(pla_engine* eng, const void* in, const void* y_hat, const double
   PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
   PLA_HIP(hipStreamSynchronize(s));
   if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
+}
+
+// ---- LOO diagnostics (csrc/pla_diag.h) -------------------------------------------------------------------------------------------
+// pla_loo_pit's PLA_PIT_LOGLIK pipeline with the PIT kernel replaced: per block of rows, -ll (selected rows) into the ingest staging
+// d_in, the weights pass of pla_importance_weights from d_in into d_lw (it reads its input const: d_in is intact behind it), then
+// diag_wave_kernel on (d_lw, d_in, sign -1) before the next block overwrites either.
+int pla_loo_diag(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                 const int64_t* row_index, int64_t n_rows, int method, int64_t tail_count, int mem_space, void* stream, double* diag,
+                 double* elpd_i, double* ess_w, double* var_log, int64_t* n_replaced) {
+  int rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, mem_space);
+  if (rc) return rc;
+  if (n_draws < 2) return fail(PLA_ERR_ARG, "n_draws out of range (at least 2)");
+  if (stride_obs <= 0 || stride_draw <= 0) return fail(PLA_ERR_ARG, "strides must be positive");
+  if (row_index) {
+    rc = check_rows(row_index, n_rows, n_obs, mem_space);
+    if (rc) return rc;
+  }
+  const int64_t m = row_index ? n_rows : n_obs;  // rows of this call
+  const bool host = mem_space == PLA_HOST;
+  const bool in_of = host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw);
+  if (host && stride_draw != 1 && !in_of)
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST matrices need unit stride along the draws, or along the observations");
+  if (host && in_of && row_index)
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST row selection needs unit stride along the draws");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (m == 0) {
+    if (host && n_replaced) *n_replaced = 0;
+    if (!host && n_replaced) PLA_HIP(hipMemsetAsync(n_replaced, 0, sizeof(int64_t), s));
+    return PLA_OK;
+  }
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int S = (int)n_draws;
+  char route[160];
+
+  // the weights pass of a block, as pla_importance_weights sets it up
+  pla::RowsParams p{};
+  int64_t rows = staged_chunk_rows(mem_space, true, m, n_draws, esz);
+  rc = weights_block_setup(eng, method, tail_count, n_draws, esz, s, &rows, &p);
+  if (rc) return rc;
+  const size_t block_bytes = (size_t)rows * (size_t)n_draws * esz;
+  rc = grow(&eng->d_in, &eng->d_in_bytes, block_bytes);
+  if (rc) return rc;
+  if (host && in_of) {
+    rc = grow(&eng->d_slab, &eng->d_slab_bytes, block_bytes);
+    if (rc) return rc;
+  }
+  unsigned long long* d_count = nullptr;
+  double *d_diag = diag, *d_elpd = elpd_i, *d_ess = ess_w, *d_var = var_log;
+  if (host) {
+    size_t have_b = eng->d_pw_elems * sizeof(double);
+    rc = grow((void**)&eng->d_pw, &have_b, (size_t)(4 * m + PLA_AGG_COUNT) * sizeof(double));
+    eng->d_pw_elems = have_b / sizeof(double);
+    if (rc) return rc;
+    d_diag = eng->d_pw;
+    d_elpd = eng->d_pw + m;
+    d_ess = eng->d_pw + 2 * m;
+    d_var = eng->d_pw + 3 * m;
+    d_count = eng->counters + pla::kCounterPitReplaced;
+    PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  } else {
+    d_count = (unsigned long long*)n_replaced;
+    if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+  }
+
+  std::string label;
+  const size_t row_bytes = (size_t)n_draws * esz;
+  for (int64_t r0 = 0; r0 < m; r0 += rows) {
+    const int64_t nr = m - r0 < rows ? m - r0 : rows;
+    const char* prep = "";
+    if (!host) {
+      PLA_HIP(pla::launch_diag_prepare(ll, dtype, n_obs, stride_obs, stride_draw, row_index ? row_index + r0 : nullptr, r0, nr, S, eng->d_in,
+                                       d_count, s, &prep));
+    } else if (in_of) {  // the (n_draws, nr) slab as it lies, turned on the device
+      PLA_HIP(hipMemcpy2DAsync(eng->d_slab, (size_t)nr * esz, (const char*)ll + (size_t)r0 * esz, (size_t)stride_draw * esz,
+                               (size_t)nr * esz, (size_t)n_draws, hipMemcpyHostToDevice, s));
+      PLA_HIP(pla::launch_diag_prepare(eng->d_slab, dtype, nr, 1, nr, nullptr, 0, nr, S, eng->d_in, d_count, s, &prep));
+    } else {  // (the weights buffer is free until the weights pass writes it)
+      if (!row_index) {
+        PLA_HIP(hipMemcpy2DAsync(eng->d_lw, row_bytes, (const char*)ll + (size_t)r0 * (size_t)stride_obs * esz, (size_t)stride_obs * esz,
+                                 row_bytes, (size_t)nr, hipMemcpyHostToDevice, s));
+      } else {
+        for (int64_t i = 0; i < nr; ++i)
+          PLA_HIP(hipMemcpyAsync((char*)eng->d_lw + (size_t)i * row_bytes, (const char*)ll + (size_t)row_index[r0 + i] * (size_t)stride_obs * esz,
+                                 row_bytes, hipMemcpyHostToDevice, s));
+      }
+      PLA_HIP(pla::launch_diag_prepare(eng->d_lw, dtype, nr, n_draws, 1, nullptr, 0, nr, S, eng->d_in, d_count, s, &prep));
+    }
+    p.in = eng->d_in;
+    p.n_obs = nr;
+    p.diag = d_diag ? d_diag + r0 : nullptr;
+    p.lw_out = eng->d_lw;
+    PLA_HIP(pla::launch_rows(p, dtype, true, s));
+    PLA_HIP(pla::launch_diag(eng->d_lw, eng->d_in, -1.0, dtype, nr, S, n_draws, 1, n_draws, 1, d_elpd ? d_elpd + r0 : nullptr,
+                             d_ess ? d_ess + r0 : nullptr, d_var ? d_var + r0 : nullptr, s, route, (int)sizeof(route)));
+    if (r0 == 0)
+      label = std::string(prep) + " -> " + std::string(pla::last_rows_kernels()) + " -> " + route +
+              (host ? " (matrix staged in blocks)" : " per block of observations");
+    if (host) PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+  }
+  eng->last_kernels = label;
+  if (!host) return PLA_OK;
+  const size_t out_bytes = (size_t)m * sizeof(double);
+  if (diag) PLA_HIP(hipMemcpyAsync(diag, d_diag, out_bytes, hipMemcpyDeviceToHost, s));
+  if (elpd_i) PLA_HIP(hipMemcpyAsync(elpd_i, d_elpd, out_bytes, hipMemcpyDeviceToHost, s));
+  if (ess_w) PLA_HIP(hipMemcpyAsync(ess_w, d_ess, out_bytes, hipMemcpyDeviceToHost, s));
+  if (var_log) PLA_HIP(hipMemcpyAsync(var_log, d_var, out_bytes, hipMemcpyDeviceToHost, s));
+  unsigned long long h = 0;
+  PLA_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h;
+  return PLA_OK;
+}
+
+// the kernel alone on caller-supplied log weights: device matrices in place, host matrices staged in blocks (lw in d_in, ll in d_lw)
+int pla_loo_diag_weights(pla_engine* eng, const void* lw, const void* ll, int dtype, int64_t n_obs, int64_t n_draws,
+                         int64_t lw_stride_obs, int64_t lw_stride_draw, int64_t ll_stride_obs, int64_t ll_stride_draw, int mem_space,
+                         void* stream, double* elpd_i, double* ess_w, double* var_log) {
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  if (dtype != PLA_F64 && dtype != PLA_F32) return fail(PLA_ERR_ARG, "dtype must be PLA_F64 or PLA_F32");
+  if (mem_space != PLA_HOST && mem_space != PLA_DEVICE) return fail(PLA_ERR_ARG, "bad mem_space");
+  if (n_obs < 0) return fail(PLA_ERR_ARG, "n_obs < 0");
+  if (n_draws < 2 || n_draws > (int64_t)1 << 30) return fail(PLA_ERR_ARG, "n_draws out of range (at least 2)");
+  if (lw_stride_obs <= 0 || lw_stride_draw <= 0 || ll_stride_obs <= 0 || ll_stride_draw <= 0)
+    return fail(PLA_ERR_ARG, "strides must be positive");
+  if (n_obs > 0 && (!lw || !ll)) return fail(PLA_ERR_ARG, "lw / ll is NULL");
+  const bool host = mem_space == PLA_HOST;
+  if (host && (lw_stride_draw != 1 || ll_stride_draw != 1))
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST matrices need unit stride along the draws");
+  EngineCall call(eng, (hipStream_t)stream);
+  PLA_HIP(hipSetDevice(eng->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n_obs == 0) return PLA_OK;
+  const int S = (int)n_draws;
+  char route[160];
+  if (!host) {
+    PLA_HIP(pla::launch_diag(lw, ll, 1.0, dtype, n_obs, S, lw_stride_obs, lw_stride_draw, ll_stride_obs, ll_stride_draw, elpd_i, ess_w,
+                             var_log, s, route, (int)sizeof(route)));
+    eng->last_kernels = std::string(route) + " (matrices read in place)";
+    return PLA_OK;
+  }
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int64_t rows = staged_chunk_rows(mem_space, true, n_obs, n_draws, esz);
+  const size_t row_bytes = (size_t)n_draws * esz, block_bytes = (size_t)rows * row_bytes;
+  int rc = grow(&eng->d_in, &eng->d_in_bytes, block_bytes);
+  if (rc) return rc;
+  rc = grow(&eng->d_lw, &eng->d_lw_bytes, block_bytes);
+  if (rc) return rc;
+  size_t have_b = eng->d_pw_elems * sizeof(double);
+  rc = grow((void**)&eng->d_pw, &have_b, (size_t)(3 * n_obs + PLA_AGG_COUNT) * sizeof(double));
+  eng->d_pw_elems = have_b / sizeof(double);
+  if (rc) return rc;
+  double *d_elpd = eng->d_pw, *d_ess = eng->d_pw + n_obs, *d_var = eng->d_pw + 2 * n_obs;
+  for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+    const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+    PLA_HIP(hipMemcpy2DAsync(eng->d_in, row_bytes, (const char*)lw + (size_t)r0 * (size_t)lw_stride_obs * esz, (size_t)lw_stride_obs * esz,
+                             row_bytes, (size_t)nr, hipMemcpyHostToDevice, s));
+    PLA_HIP(hipMemcpy2DAsync(eng->d_lw, row_bytes, (const char*)ll + (size_t)r0 * (size_t)ll_stride_obs * esz, (size_t)ll_stride_obs * esz,
+                             row_bytes, (size_t)nr, hipMemcpyHostToDevice, s));
+    PLA_HIP(pla::launch_diag(eng->d_in, eng->d_lw, 1.0, dtype, nr, S, n_draws, 1, n_draws, 1, d_elpd + r0, d_ess + r0, d_var + r0, s, route,
+                             (int)sizeof(route)));
+    PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+  }
+  eng->last_kernels = std::string(route) + " (matrices staged in blocks)";
+  const size_t out_bytes = (size_t)n_obs * sizeof(double);
+  if (elpd_i) PLA_HIP(hipMemcpyAsync(elpd_i, d_elpd, out_bytes, hipMemcpyDeviceToHost, s));
+  if (ess_w) PLA_HIP(hipMemcpyAsync(ess_w, d_ess, out_bytes, hipMemcpyDeviceToHost, s));
+  if (var_log) PLA_HIP(hipMemcpyAsync(var_log, d_var, out_bytes, hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
   return PLA_OK;
 }
 

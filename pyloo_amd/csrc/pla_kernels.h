@@ -216,6 +216,15 @@ hipError_t launch_pit_prepare(const void* in, int dtype, int64_t stride_obs, int
 hipError_t launch_pit(const void* lw, const void* yh, const double* y, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs,
                       int64_t lw_stride_draw, int64_t yh_stride_obs, int64_t yh_stride_draw, double* pit_le, double* pit_lt,
                       hipStream_t stream, char* route, int cap);
+// LOO diagnostics (pla_diag.h).  launch_diag_prepare: launch_pit_prepare with a row gather -- out row r = -in[row_index[r]] (row_index
+// null: row row0 + r; a device list, clamped into [0, n_src) by the kernel).  launch_diag: elpd / ess_w / var_log (each may be null)
+// from the log weights and x with ll = sign * x, each matrix with its own strides; route: text for pla_engine_last_kernels.
+hipError_t launch_diag_prepare(const void* in, int dtype, int64_t n_src, int64_t stride_obs, int64_t stride_draw, const int64_t* row_index,
+                               int64_t row0, int64_t n_rows, int n_draws, void* out, unsigned long long* replaced, hipStream_t stream,
+                               const char** route);
+hipError_t launch_diag(const void* lw, const void* x, double sign, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs,
+                       int64_t lw_stride_draw, int64_t x_stride_obs, int64_t x_stride_draw, double* elpd, double* ess_w, double* var_log,
+                       hipStream_t stream, char* route, int cap);
 // leave-future-out CV (pla_lfo.h).  launch_lfo_ratios: the log ratios of one block of n_rows steps -- whole chunks of
 // lfo_chunk_rows() steps unless it is the last block -- as a contiguous (n_rows, n_draws) f64 matrix; `in` is the row of the block's
 // first step (draws contiguous), rows j < n_load of the block are read (NaN -> -1e10, counted in `replaced`, may be null); carry:

@@ -834,6 +834,78 @@ class Engine:
                                     int(tail_count), PLA_HOST, None, p(pit_le), p(pit_lt), p(diag), C.byref(nrep)))
         return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": int(nrep.value)}
 
+    # ------------------------------------------------------------------ LOO diagnostics
+    def loo_diag(self, ll, tail_count=0, method="psis", rows=None):
+        """(n_obs, n_draws) log-likelihood -> ``dict(diag, elpd_i, ess_w, var_log, n_replaced)`` (``pla_loo_diag``): the Pareto k
+        (ESS for SIS / TIS) of the leave-one-out weights, the pointwise elpd, the effective sample size ``1 / sum w^2`` of the
+        weights and the log-scale variance of the estimate, per observation.  ``rows``: optional observation indices, one output
+        entry per index.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out, nothing synchronised."""
+        mcode = METHOD_CODES[method]
+        if _is_torch_tensor(ll):
+            import torch
+
+            if ll.dim() != 2 or not ll.is_cuda:
+                raise ValueError("expected a 2-D CUDA tensor")
+            if ll.dtype not in (torch.float64, torch.float32):
+                raise TypeError(f"unsupported dtype {ll.dtype}")
+            t = self._library_layout(ll)
+            n, s = t.shape
+            dev = t.device
+            idx = None if rows is None else self._device_rows(rows, n, dev)
+            m = n if idx is None else idx.numel()
+            out = [torch.empty(m, dtype=torch.float64, device=dev) for _ in range(4)]
+            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
+            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            so = t.stride(0) if n > 1 else max(s, 1)
+            check(self._lib.pla_loo_diag(self._h, p(t), code, n, s, so, t.stride(1), p(idx), m, mcode, int(tail_count), PLA_DEVICE,
+                                         self._stream(), p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nrep)))
+            return {"diag": out[0], "elpd_i": out[1], "ess_w": out[2], "var_log": out[3], "n_replaced": nrep}
+        a = self._as_2d_host(ll, allow_obs_fastest=rows is None)
+        n, s = a.shape
+        so, sd = self._host_strides(a)
+        idx = None if rows is None else self._host_rows(rows, n)
+        m = n if idx is None else idx.size
+        out = [np.empty(m) for _ in range(4)]
+        nrep = C.c_int64(0)
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        check(self._lib.pla_loo_diag(self._h, p(a), dtype_code(a.dtype), n, s, so, sd, p(idx), m, mcode, int(tail_count), PLA_HOST, None,
+                                     p(out[0]), p(out[1]), p(out[2]), p(out[3]), C.byref(nrep)))
+        return {"diag": out[0], "elpd_i": out[1], "ess_w": out[2], "var_log": out[3], "n_replaced": int(nrep.value)}
+
+    def loo_diag_weights(self, lw, ll):
+        """Log weights of any normalisation and the log-likelihood, two (n_obs, n_draws) matrices -> ``dict(elpd_i, ess_w, var_log)``
+        (``pla_loo_diag_weights``).  The matrices are promoted to one dtype (f64 if either is) and passed with their own strides.
+        NumPy in -> NumPy out; CUDA tensors in -> CUDA tensors out, nothing synchronised."""
+        if _is_torch_tensor(lw):
+            import torch
+
+            if not _is_torch_tensor(ll) or lw.dim() != 2 or ll.shape != lw.shape or not lw.is_cuda or not ll.is_cuda:
+                raise ValueError("lw and ll must be 2-D CUDA tensors of one shape")
+            dt = torch.float64 if torch.float64 in (lw.dtype, ll.dtype) else torch.float32
+            mats = [m.to(dt) for m in (lw, ll)]
+            mats = [m if min(m.stride()) > 0 else m.contiguous() for m in mats]
+            n, s = mats[0].shape
+            out = [torch.empty(n, dtype=torch.float64, device=mats[0].device) for _ in range(3)]
+            p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+            code = _capi.PLA_F64 if dt == torch.float64 else _capi.PLA_F32
+            check(self._lib.pla_loo_diag_weights(self._h, p(mats[0]), p(mats[1]), code, n, s, mats[0].stride(0), mats[0].stride(1),
+                                                 mats[1].stride(0), mats[1].stride(1), PLA_DEVICE, self._stream(), p(out[0]), p(out[1]),
+                                                 p(out[2])))
+            return {"elpd_i": out[0], "ess_w": out[1], "var_log": out[2]}
+        mats = [np.asarray(lw), np.asarray(ll)]
+        if mats[0].ndim != 2 or mats[1].shape != mats[0].shape:
+            raise ValueError("lw and ll must be 2-D arrays of one shape")
+        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
+        mats = [self._as_2d_host(m if m.dtype == dt else m.astype(dt)) for m in mats]
+        n, s = mats[0].shape
+        out = [np.empty(n) for _ in range(3)]
+        p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        so = [m.strides[0] // m.itemsize if n > 1 else s for m in mats]
+        check(self._lib.pla_loo_diag_weights(self._h, p(mats[0]), p(mats[1]), dtype_code(dt), n, s, so[0], 1, so[1], 1, PLA_HOST, None,
+                                             p(out[0]), p(out[1]), p(out[2])))
+        return {"elpd_i": out[0], "ess_w": out[1], "var_log": out[2]}
+
     # ------------------------------------------------------------------ leave-future-out CV
     def _lfo_input(self, ll):
         """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None).  A CUDA tensor with the draws or

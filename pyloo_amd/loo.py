@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 
 from ._capi import AGG_M2_LOO, AGG_N_HIGH, AGG_MIN_DIAG, AGG_SUM_LOO, AGG_SUM_LPPD
-from .base import ISMethod, parse_method, tail_count_for
+from .base import ISMethod, check_reff_vector, is_reff_vector, parse_method, tail_buckets, tail_count_for
 from .elpd import ELPDData
 from .engine import _is_torch_tensor, get_engine
 from .rcparams import rcParams
@@ -54,8 +54,72 @@ def _relative_efficiency(idata, n_samples):
     return np.hstack([ess_p[v].values.flatten() for v in ess_p.data_vars]).mean() / n_samples
 
 
+def bucketed_matrix(matrix, reff):
+    """What every front of a per-observation ``reff`` does before its first engine call: the checked vector in the memory space of
+    the matrix, the matrix with its draws contiguous (the ``rows=`` route takes no other layout without a copy per call, and none
+    at all on the host), and ``tail_buckets`` of the two."""
+    n_obs, n_samples = matrix.shape
+    r = check_reff_vector(reff, n_obs)
+    tensor = _is_torch_tensor(matrix)
+    if tensor:
+        import torch
+
+        r = r.to(matrix.device) if _is_torch_tensor(r) else torch.as_tensor(r, device=matrix.device)
+    else:
+        r = r.cpu().numpy() if _is_torch_tensor(r) else r
+        matrix = np.asarray(matrix)
+    M, buckets = tail_buckets(r, n_samples)
+    if buckets and buckets[-1][0] + 1 > n_samples:
+        raise IndexError(f"index {-buckets[-1][0] - 1} is out of bounds for axis 0 with size {n_samples}")
+    if len(buckets) > 1 and n_samples > 1:  # (one bucket: the full-matrix call, which reads every layout as it is)
+        if tensor and matrix.stride(1) != 1:
+            matrix = matrix.contiguous()
+        elif not tensor and matrix.strides[1] != matrix.itemsize:
+            matrix = np.ascontiguousarray(matrix)
+    return matrix, r, buckets
+
+
+def scatter_buckets(matrix, buckets, keys, run):
+    """``run(m, index)`` -> dict per bucket, its ``keys`` scattered into full-length float64 outputs of the kind of ``matrix``."""
+    n_obs = matrix.shape[0]
+    if _is_torch_tensor(matrix):
+        import torch
+
+        full = {k: torch.empty(n_obs, dtype=torch.float64, device=matrix.device) for k in keys}
+    else:
+        full = {k: np.empty(n_obs) for k in keys}
+    for m, index in buckets:
+        res = run(m, index)
+        for k in keys:
+            full[k][index] = res[k]
+    return full
+
+
+def _engine_pass_vector(matrix, method, reff, scale_value, good_k, distributed):
+    """The pass of a per-observation ``reff``: the observations are bucketed by their own tail count and every bucket goes through
+    the ``rows=`` route of the unchanged kernels; a single bucket is the full-matrix call itself."""
+    if distributed:
+        raise NotImplementedError("a per-observation reff is not available with distributed=True")
+    if method != ISMethod.PSIS:
+        raise ValueError(f"a per-observation reff sets the tail length of PSIS; method '{method.value}' has no tail: pass a float")
+    matrix, _, buckets = bucketed_matrix(matrix, reff)
+    eng = get_engine(matrix.device.index if _is_torch_tensor(matrix) else None)
+    if len(buckets) <= 1:
+        M = buckets[0][0] if buckets else 0
+        res = eng.psis_loo(matrix, M, method.value, scale_value, good_k)
+        return res, res["agg"]
+    res = scatter_buckets(matrix, buckets, ("diag", "loo_i", "lppd_i"),
+                          lambda m, index: eng.psis_loo(matrix, m, method.value, scale_value, good_k, pointwise=True, aggregate=False,
+                                                        rows=index))
+    res["agg"] = eng.reduce_pointwise(res["diag"], res["loo_i"], res["lppd_i"], good_k)
+    return res, res["agg"]
+
+
 def _engine_pass(matrix, method, reff, scale_value, good_k, distributed=False, group=None):
     """One fused pass + (optionally) the cross-rank merge.  Returns (pointwise dict, agg ndarray)."""
+    if is_reff_vector(reff):
+        res, a = _engine_pass_vector(matrix, method, reff, scale_value, good_k, distributed)
+        return res, (a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a))
     n_samples = matrix.shape[-1]
     M = tail_count_for(n_samples, reff) if method == ISMethod.PSIS else 0
     if method == ISMethod.PSIS and M + 1 > n_samples:
@@ -168,7 +232,9 @@ def loo_from_matrix(log_likelihood, reff=1.0, scale=None, method="psis", pointwi
     copies, the matrix is read exactly once).  With ``distributed=True`` (and
     ``torch.distributed`` initialised) every rank passes ITS OWN block of observations; the
     aggregates are merged with a single all-reduce and are identical on all ranks, pointwise
-    outputs stay sharded.
+    outputs stay sharded.  ``reff`` is a float or a vector with one relative efficiency per
+    observation (NumPy or CUDA tensor, e.g. ``relative_eff_from_matrix``'s output): every
+    observation then has its own tail length (PSIS only, not with ``distributed=True``).
     """
     method = parse_method(method)
     scale, scale_value = _scale_value(scale)

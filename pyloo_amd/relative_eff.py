@@ -1,5 +1,6 @@
 """``relative_eff()`` -- the relative MCMC efficiency of the likelihood, one value per observation, on the HIP engine: the
-``r_eff = relative_eff(exp(log_lik), chain_id)`` of R-loo whose mean is the ``reff`` every PSIS entry point here takes.  The
+``r_eff = relative_eff(exp(log_lik), chain_id)`` of R-loo: the ``reff`` that ``loo``, ``loo_from_matrix`` and ``loo_diagnostics``
+take as a vector (every observation then has its own tail length) and whose mean the other PSIS entry points take.  The
 reference has no such function (its ``reff=None`` asks ArviZ for the ESS of the posterior).
 
 The estimator is Stan's effective sample size for the mean (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021; Geyer 1992's
@@ -7,10 +8,12 @@ initial positive and monotone sequences) without rank normalisation, on ``exp(lo
 states it in full.  ``split=False`` is R-loo's ``relative_eff``, ``split=True`` the split-chain convention of ArviZ / posterior.
 
     r = pl.relative_eff_from_matrix(ll, n_chains=4)
-    res = pl.loo_from_matrix(ll, reff=float(r.mean()))
+    res = pl.loo_from_matrix(ll, reff=r)
+    d = pl.loo_diagnostics_from_matrix(ll, reff=r)   # n_eff and the Monte Carlo error of every loo_i (loo_diagnostics.py)
 
-Out of scope: per-observation tail lengths inside the PSIS kernels (the engine takes one), rank-normalised / bulk / tail ESS,
-MCSE, and any change to what ``reff=None`` does.
+Out of scope: per-observation tail lengths inside the PSIS kernels (the engine takes one per pass: a vector is run bucket by
+bucket of equal tail length, ``base.tail_buckets``), rank-normalised / bulk / tail ESS, and any change to what ``reff=None``
+does in ``loo``.
 """
 
 import numpy as np
