@@ -1156,7 +1156,7 @@ __device__ __forceinline__ void wave_select_split(const FastParams& F, SM& sm, c
   // ---- candidates at / above the boundary bin -> sa, grouped by bin (descending bins): all the slot requests at once -----
   // (the candidates are read from the list a second time rather than held in registers across the scan: that stretch is where
   // the kernel's register count peaks, and sixteen registers less there let the fit kernel of the previous block of
-  // observations run beside this kernel -- pla_capi.hip, pipelined pass)
+  // observations run beside this kernel -- pla_capi_loo.hip, pipelined pass)
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int u = 0; u < U; ++u) {

@@ -67,6 +67,70 @@ def test_argument_errors_are_status_codes(lib):
     assert lib.pla_engine_set_timing(None, 1) == -1
     assert lib.pla_fill_synthetic(None, None, 0, 1, 1, 0, 1, 0.1, 0.5, 0.0, 0.0, None) == -1
     assert lib.pla_last_error()
+    # ... every one: each exported call that takes an engine, with a NULL engine and otherwise small, plausible arguments (f64,
+    # PLA_HOST, PSIS; 2 observations x 16 draws, draws fastest; every other pointer at 64 zeroed words, which are valid index
+    # lists too).  The calls that check the engine last get that far.
+    buf = (C.c_int64 * 64)()
+    b = C.cast(buf, C.c_void_p)
+    mat = (b, 0, 2, 16, 16, 1)  # matrix, dtype, n_obs, n_draws, stride_obs, stride_draw
+    calls = {
+        "pla_psis_loo": (*mat, 0, 4, 1.0, 0.7, 0, None, b, b, b, b),
+        "pla_psis_loo_rows": (*mat, b, 1, 0, 4, 1.0, 0.7, 0, None, b, b, b, b),
+        "pla_psis_loo_groups": (*mat, b, b, 1, 0, 4, 1.0, 0.7, 0, None, b, b, b, b, b),
+        "pla_psis_loo_draws": (*mat, b, 8, 0, 4, 1.0, 0.7, 0, None, b, b, b, b, b),
+        "pla_importance_weights": (*mat, 0, 4, 0, None, b, b),
+        "pla_reduce_pointwise": (b, b, b, 2, 0.7, 0, None, b),
+        "pla_waic": (*mat, 1.0, 0, None, b, b, b, b),
+        "pla_waic_rows": (*mat, b, 1, 1.0, 0, None, b, b, b, b),
+        "pla_e_loo": (b, b, b, 0, 2, 16, 16, 1, 5, 0, None, b, b, b, b, b),
+        "pla_e_loo_quantiles": (b, b, 0, 2, 16, 16, 1, b, 0, 0, None, b),
+        "pla_engine_set_frozen": (1,),
+        "pla_engine_set_timing": (1,),
+        "pla_engine_kernel_ms": (None, None),
+        "pla_engine_first_kernel_ms": (None, None),
+        "pla_engine_last_kernels": (C.create_string_buffer(64), 64),
+        "pla_engine_stream_stats": (None,),
+        "pla_engine_set_compare_grid": (4,),
+        "pla_engine_set_nonfactor_route": (0,),
+        "pla_engine_set_nonfactor_grid": (4,),
+        "pla_engine_set_mixis_grid": (4,),
+        "pla_engine_set_ess_grid": (4,),
+        "pla_fill_synthetic": (b, 0, 2, 16, 0, 1, 0.1, 0.5, 0.0, 0.0, None),
+        "pla_fill_synthetic_chains": (b, 0, 2, 16, 0, 1, 4, 0.5, 0.1, 0.1, 0.5, None),
+        "pla_aggregate_pack": (b, 0, 1, b, None),
+        "pla_aggregate_merge": (b, 1, b, None),
+        "pla_group_sum": (*mat, b, b, 1, 0, None, b, b),
+        "pla_gather_draws": (*mat, b, 8, 0, None, b, b),
+        "pla_compare_moments": (b, 0, 2, 16, 16, 0, 0, None, b),
+        "pla_stacking_eval": (b, 0, 2, 16, 16, 1.0, b, 0, None, b),
+        "pla_bb_bootstrap": (b, 0, 2, 16, 16, 1.0, 4, 1.0, 7, 0, None, b),
+        "pla_bb_gamma_draws": (7, 1.0, 2, 16, 0, None, b),
+        "pla_nonfactor_loglik": (b, b, b, b, 0, 2, 4, 2, 4, 0, 0, None, b, 4, 1, b),
+        "pla_kfold_lme": (b, b, b, b, b, 1, 0, 0, b, b, b, 1, 1, None, b, 1, b),
+        "pla_kfold_reduce": (b, b, 2, 1.0, b, 1, None, b, b, b),
+        "pla_mm_moments": (b, b, 1, 16, 2, 0, None, b, b),
+        "pla_mm_transform": (b, 0, b, None, None, None, b, 1, 16, 2, 0, 16, None, b),
+        "pla_mm_ratios": (0, b, b, b, None, 1, 16, None, b),
+        "pla_mixis_draw_lse": (*mat, 0, None, b, b),
+        "pla_mixis_loo": (*mat, None, 1.0, 0, None, b, b),
+        "pla_loo_pit": (b, b, b, 0, 2, 16, 16, 1, 16, 1, 0, 0, 4, 0, None, b, b, b, b),
+        "pla_loo_diag": (*mat, None, 0, 0, 4, 0, None, b, b, b, b, b),
+        "pla_loo_diag_weights": (b, b, 0, 2, 16, 16, 1, 16, 1, 0, None, b, b, b),
+        "pla_lfo_ratios": (*mat, 0, 2, 0, None, b, b),
+        "pla_lfo": (*mat, 0, 1, 1, 0, 4, 0.7, 0, None, b, b, b, b),
+        "pla_relative_eff": (*mat, 2, 0, 0, None, b, b),
+    }
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pyloo_amd.h")).read(), flags=re.S)
+    takes_engine = set(re.findall(r"\b(pla_[a-z0-9_]+)\s*\(\s*pla_engine\s*\*", text)) - {"pla_engine_destroy"}
+    assert takes_engine == set(calls), sorted(takes_engine ^ set(calls))
+    lib.pla_tail_count(0, 1.0, None)  # (leaves its own message: the calls below must each replace it)
+    marker = lib.pla_last_error()
+    for name, args in sorted(calls.items()):
+        assert len(args) + 1 == len(getattr(lib, name).argtypes), name
+        assert getattr(lib, name)(None, *args) == -1, name  # PLA_ERR_ARG
+        msg = lib.pla_last_error()
+        assert msg and msg != marker, name
+        assert b"ngine" in msg, (name, msg)
 
 
 def test_shipped_library_reads_only_the_path_selectors(lib, monkeypatch):
@@ -86,7 +150,7 @@ def test_shipped_library_reads_only_the_path_selectors(lib, monkeypatch):
     monkeypatch.setenv("PLA_FORCE_PATH", "1")
     assert _capi.env_overrides() == "PLA_PIPE=0 PLA_FORCE_PATH=1"
     assert lib.pla_env_overrides(None, 0) == -1 and lib.pla_engine_stream_stats(None, None) == -1
-    # every getenv of the library: the one helper behind env_flag / exp_flag (pla_launch.h) and the selectors of pla_capi.hip
+    # every getenv of the library: the one helper behind env_flag / exp_flag (pla_launch.h) and the selectors of the pla_capi_*.hip units
     allowed = {"PLA_PIPE", "PLA_STREAM_PATIENCE_US", "PLA_FORCE_PATH", "PLA_INGEST_TRANSPOSE", "PLA_INGEST_BLOCK_MB"}
     csrc = os.path.join(ROOT, "pyloo_amd", "csrc")
     for f in sorted(os.listdir(csrc)):

@@ -411,7 +411,7 @@ def test_aggregate_pack_and_merge_kernels(eng):
 
 
 def test_device_path_runs_in_row_blocks(eng):
-    """More than 2^20 observations: the device path runs block by block (bounded hand-over buffer, pla_capi.hip).  Rows on
+    """More than 2^20 observations: the device path runs block by block (bounded hand-over buffer, pla_capi_loo.hip).  Rows on
     both sides of the block boundary equal a separate pass over just those rows bit for bit, the aggregate equals the sum of
     the pointwise values, and the row-index flavour (``pla_psis_loo_rows``) walks its index list in the same blocks."""
     import math

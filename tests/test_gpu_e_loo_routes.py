@@ -410,7 +410,7 @@ def test_grid_stride(eng, torch, monkeypatch, dt, S, N):
 
 # ---- (d) host staging blocks ------------------------------------------------------------------------------------------------
 def test_host_staging_blocks(eng, torch):
-    """A host call is staged in blocks of 2^29 bytes of rows (pla_capi.hip): at S = 8192 f64 that is 8192 rows a block, and
+    """A host call is staged in blocks of 2^29 bytes of rows (pla_capi_loo.hip): at S = 8192 f64 that is 8192 rows a block, and
     8192 + 64 rows span two."""
     S, per = 8192, (1 << 29) // (8 * 8192)
     N = per + 64
