@@ -602,7 +602,24 @@ int pla_loo_diag_weights(pla_engine *eng, const void *lw, const void *ll, int dt
  * step of a block needs); other strides return PLA_ERR_UNSUPPORTED.  PLA_DEVICE: everything is enqueued on `stream`, the outputs,
  * first_high and n_replaced (one int64 each) are device pointers, and nothing is allocated once the workspace fits
  * (pla_engine_set_frozen).  PLA_HOST: the matrix is staged in 1 GiB blocks and the call returns when the results are there.
+ *
+ * BACKWARD MODE of pla_lfo (the algorithm as the paper states it; csrc/pla_lfo_bw.h): method = PLA_PSIS | PLA_LFO_BACKWARD.  The low
+ * byte of `method` stays the IS method (PLA_SIS / PLA_TIS with the flag: PLA_ERR_UNSUPPORTED).  `first` then carries `last`, the
+ * number of observations the fit SAW (1 .. n_obs; a walk begins with the fit to all of them, last = n_obs), and ll holds all n_obs
+ * rows under its draws -- rows r >= last are the conditional terms log p(y_r | y_<r, theta_s), which the caller supplies.  The
+ * steps go DOWN from t_0 = min(last, n_obs - horizon):  t_j = t_0 - j, j = 0 .. n_steps - 1, 1 <= n_steps <= t_0 + 1, and
+ *     f_j[s]  = ll[t_j, s] + ... + ll[t_j + horizon - 1, s]  (in that order)      lr_j[s] = - sum_{r = t_j}^{last - 1} ll[r, s]
+ *     t_j = last:  elpd_i[j] = logsumexp_s(f_j) - log n_draws, diag[j] = 0        (exact; only j = 0 can be, when last <= n_obs - horizon)
+ *     t_j < last:  (lw_j, diag[j]) = PSIS(lr_j), elpd_i[j] = logsumexp_s(lw_j + f_j) - logsumexp_s(lw_j)
+ * *first_high = the smallest j >= j_min with diag[j] > k_threshold, else n_steps; j_min = 1 when step 0 is exact, else 0 (with
+ * last = n_obs step 0 has already removed `horizon` rows and may itself be above the threshold).  NaN entries are counted once each
+ * over rows [t_{n_steps - 1}, t_0 + horizon).  The summation rule is the one above ANCHORED AT THE FIT: with a_q = ll[last - 1 - q]
+ * (the same rows, walked downward), P[q] built from a as lr is built from ll[first + .] above (P[0] = 0, P[q] = carry[q / C] +
+ * local[q]), lr_j = -P[last - t_j]; it depends on last - t_j and C alone.  Bad geometry returns PLA_ERR_ARG with a text in
+ * pla_last_error.  Layouts, memory spaces, the block pipeline and the frozen-engine rule are those of forward mode; the horizon - 1
+ * extra rows of a staged block lie above its highest row.  pla_lfo_ratios has no backward mode.
  */
+#define PLA_LFO_BACKWARD 0x100
 int pla_lfo_ratios(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
                    int64_t first, int64_t n_steps, int mem_space, void *stream, double *out, int64_t *n_replaced /* may be NULL */);
 int pla_lfo(pla_engine *eng, const void *ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,

@@ -16,6 +16,7 @@ ABI_VERSION = 7
 PLA_MVN_NORMAL, PLA_MVN_STUDENT_T = 0, 1
 PLA_PIT_LOGLIK, PLA_PIT_LOG_WEIGHTS = 0, 1  # input_kind of pla_loo_pit
 PLA_ESS_LOG, PLA_ESS_SPLIT, PLA_ESS_CAP = 1, 2, 4  # flags of pla_relative_eff
+PLA_LFO_BACKWARD = 0x100  # OR-ed into the method of pla_lfo: backward mode, `first` carries `last`
 PLA_NONFACTOR_MAX_OBS = 1024
 # status word of a draw of pla_nonfactor_loglik
 NF_GENERAL, NF_SINGULAR, NF_NONFINITE, NF_DF_NONPOS, NF_BETA_NONFINITE, NF_CLAMPED = 1, 2, 4, 8, 16, 32

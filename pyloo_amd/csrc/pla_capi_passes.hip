@@ -631,6 +631,164 @@ static int lfo_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, i
   return PLA_OK;
 }
 
+// Backward mode (csrc/pla_lfo_bw.h): the same pipeline in descending row order.  A block is whole chunks of q = last - t (the sums
+// begin at q = 0, the fit; the steps at q0 = last - t_0, so the first q0 <= M values of q are no step and only feed the sums); its
+// ratios go to d_in compact in q, and the weights pass begins at the block's first step.  A staged block holds the rows [lo, hi]
+// it touches in ascending order in d_pit: down to the row below its lowest step (the one that completes its last chunk's total;
+// the last block stops at its lowest step), up to the end of its highest step's window -- the M - 1 extra rows lie on the side
+// already visited.
+static int lfo_bw_impl(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
+                       int64_t last, int64_t n_steps, int64_t horizon, int64_t tail_count, double k_threshold, int mem_space, void* stream,
+                       double* diag, double* elpd_i, int64_t* first_high, int64_t* n_replaced) {
+  const bool host = mem_space == PLA_HOST;
+  const bool in_of = host && host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw);
+  const bool dev_of = obs_fastest_device(mem_space, nullptr, n_obs, n_draws, stride_obs, stride_draw);
+  if (stride_draw != 1 && !in_of && !dev_of)
+    return fail(PLA_ERR_UNSUPPORTED, "the matrix needs unit stride along the draws, or along the observations (stride_draw >= n_obs)");
+  if (stride_draw == 1 && n_obs > 1 && stride_obs < n_draws) return fail(PLA_ERR_ARG, "stride_obs is smaller than n_draws");
+  PLA_ENGINE_CALL(eng, stream);
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int S = (int)n_draws;
+  const int64_t C = pla::lfo_chunk_rows();
+  const int64_t t0 = last < n_obs - horizon ? last : n_obs - horizon;
+  const int64_t q0 = last - t0;       // 0 .. horizon: the q of step 0
+  const int64_t n_q = q0 + n_steps;   // the q of the pass: 0 .. n_q - 1
+  const bool staged = host || dev_of;
+
+  // q per block: the staging's size in f64 ratios, whole chunks
+  int64_t rows = staged_chunk_rows(mem_space, true, n_q, n_draws, sizeof(double));
+  const bool split = lw_split_route(PLA_PSIS, n_draws, tail_count, &rows);  // (long rows, as in pla_importance_weights)
+  if (rows < n_q) rows = rows / C * C < C ? C : rows / C * C;
+  if (rows > n_q) rows = n_q;
+  const int64_t chunks = (rows + C - 1) / C;
+  const size_t block_bytes = (size_t)rows * (size_t)n_draws * sizeof(double);
+  int rc = eng->d_lfo.reserve((size_t)(chunks + 1) * (size_t)n_draws * sizeof(double));
+  if (rc) return rc;
+  double* run = eng->d_lfo.as<double>();
+  double* carry = run + n_draws;
+  rc = eng->d_in.reserve(block_bytes);
+  if (rc) return rc;
+  if (staged) {
+    const size_t stage_bytes = (size_t)(rows + horizon) * (size_t)n_draws * esz;
+    rc = eng->d_pit.reserve(stage_bytes);
+    if (rc) return rc;
+    if (in_of) {
+      rc = eng->d_slab.reserve(stage_bytes);
+      if (rc) return rc;
+    }
+  }
+  pla::RowsParams p{};
+  p.n_draws = S;
+  p.method = PLA_PSIS;
+  p.tail_count = (int)tail_count;
+  p.tail_cap = pow2_at_least(p.tail_count);
+  p.scale_value = 1.0;
+  p.counters = eng->counters;
+  p.stride_obs = n_draws;
+  p.stride_draw = 1;
+  PLA_HIP(hipMemsetAsync(eng->counters, 0, pla::kCountersPerCall * sizeof(unsigned long long), s));
+  rc = eng->d_slow.reserve((size_t)rows * sizeof(unsigned));
+  if (rc) return rc;
+  p.slow_list = eng->d_slow.as<unsigned>();
+  rc = ensure_l1_table(eng, tail_count, s, &p.l1_table);
+  if (rc) return rc;
+  if (split) {
+    rc = lw_split_workspace(eng, tail_count, rows, &p);
+    if (rc) return rc;
+  }
+  rc = eng->d_lw.reserve(block_bytes);
+  if (rc) return rc;
+  // outputs: the caller's device arrays, or engine memory (a host call; k when the caller wants first_high without it)
+  double *d_diag = diag, *d_elpd = elpd_i;
+  unsigned long long* d_count = (unsigned long long*)n_replaced;
+  long long* d_high = (long long*)first_high;
+  if (host) {
+    d_count = eng->counters + pla::kCounterLfoReplaced;
+    d_high = (long long*)(eng->counters + pla::kCounterLfoFirstHigh);
+  }
+  HostOutputs out(eng, s);  // (its own two counters are the call's business: zeroed and read below)
+  if (host || (!diag && first_high)) {
+    rc = out.reserve(2, n_steps);
+    if (rc) return rc;
+    d_diag = out.col(0);
+    if (host) d_elpd = out.col(1);
+  }
+  if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  PLA_HIP(hipMemsetAsync(run, 0, (size_t)n_draws * sizeof(double), s));
+
+  std::string label;
+  char route[160];
+  for (int64_t qb = 0; qb < n_q; qb += rows) {
+    const int64_t nq = n_q - qb < rows ? n_q - qb : rows;
+    const bool last_block = qb + nq == n_q;
+    const int64_t skip = q0 > qb ? (q0 - qb < nq ? q0 - qb : nq) : 0;  // q of the block before the first step of the pass
+    const int64_t nb = nq - skip;                                      // steps of the block
+    const int64_t j0 = qb + skip - q0;                                 // ... the first of them
+    const int64_t n_load = last_block ? nq - 1 : nq;                   // (the last step's own row enters no sum)
+    const int64_t top = last - 1 - qb;                                 // the row of the block's first q (read when n_load > 0)
+    const int64_t t_first = last - qb - skip;                          // the row of the block's first step
+    const int64_t lo = last - qb - nq + (last_block ? 1 : 0);          // >= 0: the lowest row the block touches
+    int64_t hi = nb > 0 ? t_first + horizon - 1 : top;                 // <= n_obs - 1: the highest
+    if (hi < top) hi = top;
+    const int64_t n_stage = hi - lo + 1;                               // <= nq + horizon
+    const char* base = (const char*)ll;
+    int64_t blk_so = stride_obs, row0 = 0;
+    if (staged) {
+      if (n_stage > 0) {
+        if (dev_of) {
+          PLA_HIP(pla::launch_transpose_rows(ll, dtype, stride_draw, lo, n_stage, S, eng->d_pit.p, s));
+        } else if (in_of) {  // the (n_draws, n_stage) slab as it lies, turned on the device
+          rc = upload_slab(ll, lo, n_stage, stride_draw, n_draws, esz, eng->d_slab.p, s);
+          if (rc) return rc;
+          PLA_HIP(pla::launch_transpose_rows(eng->d_slab.p, dtype, n_stage, 0, n_stage, S, eng->d_pit.p, s));
+        } else {
+          rc = upload_rows(ll, nullptr, lo, n_stage, stride_obs, n_draws, esz, eng->d_pit.p, s);
+          if (rc) return rc;
+        }
+      }
+      base = (const char*)eng->d_pit.p;
+      blk_so = n_draws;
+      row0 = lo;
+    }
+    // (a row no kernel reads may lie one below the matrix or the staged block: the address is formed, never followed)
+    const void* scan_in = base + (top - row0) * blk_so * (int64_t)esz;
+    const void* step_in = base + (t_first - row0) * blk_so * (int64_t)esz;
+    const char* scan = "";
+    PLA_HIP(pla::launch_lfo_bw_ratios(scan_in, dtype, blk_so, S, nq, n_load, last_block, nb > 0, carry, run, eng->d_in.as<double>(), s,
+                                      &scan));
+    if (nb > 0) {
+      p.in = eng->d_in.as<double>() + (size_t)skip * (size_t)n_draws;  // (behind the q that are no step)
+      p.n_obs = nb;
+      p.diag = d_diag ? d_diag + j0 : nullptr;
+      p.lw_out = eng->d_lw.p;
+      {
+        TimedLaunch t(eng, s);
+        PLA_HIP(pla::launch_rows(p, PLA_F64, true, s));
+      }
+      PLA_HIP(pla::launch_lfo_bw_predict(eng->d_lw.as<const double>(), step_in, dtype, blk_so, nb, S, (int)horizon, j0 == 0, q0 == 0,
+                                         d_diag ? d_diag + j0 : nullptr, d_elpd ? d_elpd + j0 : nullptr, d_count, s, route,
+                                         (int)sizeof(route)));
+      if (j0 == 0)
+        label = std::string(dev_of ? "transpose_rows_kernel -> " : "") + scan + " + lfo_carry_kernel -> " + pla::last_rows_kernels() +
+                " -> " + route + (host ? " (matrix staged in blocks)" : " per block of steps");
+    }
+    if (host) PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+  }
+  eng->last_kernels = label;
+  if (d_high) PLA_HIP(pla::launch_lfo_bw_first_high(d_diag, n_steps, q0 == 0 ? 1 : 0, k_threshold, d_high, s));
+  if (!host) return PLA_OK;
+  rc = out.copy_back({diag, elpd_i});
+  if (rc) return rc;
+  unsigned long long h_count = 0;
+  long long h_high = n_steps;
+  PLA_HIP(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipMemcpyAsync(&h_high, d_high, sizeof(h_high), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (n_replaced) *n_replaced = (int64_t)h_count;
+  if (first_high) *first_high = (int64_t)h_high;
+  return PLA_OK;
+}
+
 static int lfo_check(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw,
                      int64_t first, int64_t n_steps, int64_t last_row_margin, int mem_space) {
   // (the engine last: an argument error is reported as such with or without one)
@@ -660,10 +818,33 @@ int pla_lfo_ratios(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, in
 int pla_lfo(pla_engine* eng, const void* ll, int dtype, int64_t n_obs, int64_t n_draws, int64_t stride_obs, int64_t stride_draw, int64_t first,
             int64_t n_steps, int64_t horizon, int method, int64_t tail_count, double k_threshold, int mem_space, void* stream, double* diag,
             double* elpd_i, int64_t* first_high, int64_t* n_replaced) {
+  const bool backward = (method & ~0xFF) == PLA_LFO_BACKWARD;  // (the low byte is the IS method; any other high bit is a bad method)
+  if (backward) method &= 0xFF;
   if (method != PLA_PSIS && method != PLA_SIS && method != PLA_TIS) return fail(PLA_ERR_ARG, "bad method");
   if (method != PLA_PSIS) return fail(PLA_ERR_UNSUPPORTED, "method: leave-future-out CV takes PLA_PSIS only");
   if (horizon < 1) return fail(PLA_ERR_ARG, "horizon < 1");
   if (k_threshold != k_threshold) return fail(PLA_ERR_ARG, "k_threshold is NaN");
+  if (backward) {  // `first` carries `last`, the observations the fit saw; the steps go down from t_0 = min(last, n_obs - horizon)
+    const int64_t last = first;
+    int rc = check_types(dtype, mem_space);  // (in the order of lfo_check, the engine last)
+    if (rc) return rc;
+    if (n_obs < 1) return fail(PLA_ERR_ARG, "n_obs < 1");
+    rc = check_n_draws(n_draws, 2);
+    if (rc) return rc;
+    if (stride_obs <= 0 || stride_draw <= 0) return fail(PLA_ERR_ARG, "strides must be positive");
+    if (!ll) return fail(PLA_ERR_ARG, "ll is NULL");
+    if (last < 1 || last > n_obs) return fail(PLA_ERR_ARG, "last (passed as first) out of range (1 .. n_obs)");
+    if (horizon > n_obs) return fail(PLA_ERR_ARG, "horizon exceeds n_obs");
+    const int64_t t0 = last < n_obs - horizon ? last : n_obs - horizon;
+    if (n_steps < 1 || n_steps > t0 + 1)
+      return fail(PLA_ERR_ARG, "n_steps out of range: 1 .. %lld for n_obs %lld, last %lld, horizon %lld", (long long)(t0 + 1),
+                  (long long)n_obs, (long long)last, (long long)horizon);
+    if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+    rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, mem_space);
+    if (rc) return rc;
+    return lfo_bw_impl(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, last, n_steps, horizon, tail_count, k_threshold, mem_space,
+                       stream, diag, elpd_i, first_high, n_replaced);
+  }
   int rc = lfo_check(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, first, n_steps, horizon, mem_space);
   if (rc) return rc;
   rc = check_common(eng, ll, dtype, n_obs, n_draws, stride_obs, stride_draw, method, tail_count, mem_space);

@@ -38,6 +38,11 @@ static hipError_t launch_lfo_scan_typed(LfoScanParams p, int64_t n_totals, doubl
   return hipSuccess;
 }
 
+hipError_t launch_lfo_carry(double* carry, double* run, int64_t n_chunks, int64_t n_totals, int n_draws, hipStream_t stream) {
+  PLA_LFO_LAUNCH(lfo_carry_kernel, lfo_grid((n_draws + 255) / 256, (int64_t)1 << 22), 256, carry, run, n_chunks, n_totals, n_draws);
+  return hipSuccess;
+}
+
 hipError_t launch_lfo_ratios(const void* in, int dtype, int64_t stride_obs, int n_draws, int64_t n_rows, int64_t n_load, bool last_block,
                              double* carry, double* run, double* out, unsigned long long* replaced, hipStream_t stream,
                              const char** route) {

@@ -239,6 +239,20 @@ hipError_t launch_lfo_predict(const double* lw, const void* ll, int dtype, int64
                               int n_draws, int horizon, bool pass_start, double* diag, double* elpd, unsigned long long* replaced,
                               hipStream_t stream, char* route, int cap);
 hipError_t launch_lfo_first_high(const double* diag, int64_t n_steps, double threshold, long long* out, hipStream_t stream);
+// totals -> carries of a block's chunks in place, continued through run (lfo_carry_kernel alone: backward mode launches it between its scans)
+hipError_t launch_lfo_carry(double* carry, double* run, int64_t n_chunks, int64_t n_totals, int n_draws, hipStream_t stream);
+// ... backward mode (pla_lfo_bw.h): a block is n_rows values of q = last - t, whole chunks unless it is the last; `in` is the row
+// last - 1 - q of its first q and the rows are walked DOWNWARD (row of local q: in - q stride_obs, read for q < n_load); out holds
+// -(carry + local) of its q, compact (not launched without `write`: a block before the first step only passes its carry on).  launch_lfo_bw_predict: `ll` is row t of the block's first step, step
+// j lies j rows below it and its window goes upward; pass_start: step 0 counts its whole window, exact0: and is the fit's own step.
+// launch_lfo_bw_first_high: the smallest j >= j_min above the threshold, else n_steps.
+hipError_t launch_lfo_bw_ratios(const void* in, int dtype, int64_t stride_obs, int n_draws, int64_t n_rows, int64_t n_load, bool last_block,
+                                bool write, double* carry, double* run, double* out, hipStream_t stream, const char** route);
+hipError_t launch_lfo_bw_predict(const double* lw, const void* ll, int dtype, int64_t ll_stride_obs, int64_t n_steps, int n_draws,
+                                 int horizon, bool pass_start, bool exact0, double* diag, double* elpd, unsigned long long* replaced,
+                                 hipStream_t stream, char* route, int cap);
+hipError_t launch_lfo_bw_first_high(const double* diag, int64_t n_steps, int64_t j_min, double threshold, long long* out,
+                                    hipStream_t stream);
 // relative MCMC efficiency (pla_ess.h): r_eff of n_rows rows (draws contiguous, any row stride) of n_src_chains chains of n_src draws,
 // chain major.  ws: ess_grid_for(...) slots of the analysed draws in doubles when they exceed ess_lds_max_draws(), else unused;
 // grid_cap: 0 or a cap on the workgroups; invalid: device counter of the NaN results (may be null, never zeroed here).

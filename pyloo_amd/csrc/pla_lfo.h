@@ -177,6 +177,7 @@ __global__ __launch_bounds__(256) void lfo_scan_kernel(LfoScanParams P) {
   if constexpr (WRITE) lfo_count(P.replaced, n_nan);
 }
 
+#ifndef PLA_LFO_HELPERS_ONLY  // (pla_lfo_bw.h takes the __device__ helpers and the templates; a second unit must not define these)
 // carry[c] = run + total[0] + ... + total[c - 1] in place of total[c]; run += the n_totals totals there are (the last chunk of the
 // last block has none)
 __global__ __launch_bounds__(256) void lfo_carry_kernel(double* carry, double* run, int64_t n_chunks, int64_t n_totals, int n_draws) {
@@ -192,6 +193,7 @@ __global__ __launch_bounds__(256) void lfo_carry_kernel(double* carry, double* r
   }
   run[d] = r;
 }
+#endif
 
 // ---- predict: a wavefront per step ------------------------------------------------------------------------------------------------
 // lane's vector at draw `base` of a row of lw (f64, unit stride); CLAMP: -inf past the row (such a lane reads the row's last vector
@@ -403,6 +405,7 @@ __global__ __launch_bounds__(kWave * kLfoWaves) __attribute__((amdgpu_waves_per_
   lfo_count(P.replaced, n_nan);
 }
 
+#ifndef PLA_LFO_HELPERS_ONLY
 // ---- the first step above the threshold -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void lfo_first_high_kernel(const double* diag, int64_t n_steps, double threshold, long long* out) {
   __shared__ unsigned long long best;
@@ -418,5 +421,6 @@ __global__ __launch_bounds__(256) void lfo_first_high_kernel(const double* diag,
   __syncthreads();
   if (threadIdx.x == 0) *out = (long long)best;
 }
+#endif
 
 }  // namespace pla

@@ -950,12 +950,18 @@ class Engine:
         check(self._lib.pla_lfo_ratios(self._h, p(a), code, n, s, so, sd, first, n_steps, space, stream, p(out), p(nrep)))
         return {"ratios": out, "n_replaced": nrep}
 
-    def lfo(self, ll, first, n_steps, horizon=1, tail_count=0, k_threshold=0.7, method="psis"):
+    def lfo(self, ll, first, n_steps, horizon=1, tail_count=0, k_threshold=0.7, method="psis", mode="forward"):
         """One pass of PSIS leave-future-out CV over the steps ``first .. first + n_steps - 1`` of one fit (``pla_lfo``):
         ``dict(diag, elpd_i, first_high, n_replaced)``.  ``diag[0] = 0`` (the fit's own step is exact); ``first_high`` is the
         smallest ``j >= 1`` with ``diag[j] > k_threshold``, else ``n_steps``.  NumPy in -> NumPy out (and two ints); CUDA tensor in
-        -> CUDA tensors out (``first_high`` and ``n_replaced`` one int64 each), nothing synchronised."""
-        mcode = METHOD_CODES[method]
+        -> CUDA tensors out (``first_high`` and ``n_replaced`` one int64 each), nothing synchronised.
+
+        ``mode="backward"`` (``PLA_LFO_BACKWARD``): ``first`` is ``last``, the number of observations the fit saw; step j is
+        ``t_j = min(last, n_obs - horizon) - j``, its log ratios remove the rows ``t_j .. last - 1``, only a step with ``t_j = last``
+        is exact, and ``first_high`` may be 0 when step 0 is not."""
+        if mode not in ("forward", "backward"):
+            raise ValueError(f"mode must be 'forward' or 'backward', got {mode!r}")
+        mcode = METHOD_CODES[method] | (_capi.PLA_LFO_BACKWARD if mode == "backward" else 0)
         a, n, s, so, sd, code, space, stream, device = self._lfo_input(ll)
         first, n_steps, horizon = int(first), int(n_steps), int(horizon)
         if n_steps < 1:

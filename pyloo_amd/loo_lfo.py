@@ -1,6 +1,6 @@
 """``loo_lfo()`` -- approximate leave-future-out cross-validation for time series (PSIS-LFO-CV: Buerkner, Gabry & Vehtari 2020,
-*J. Stat. Comput. Simul.* 90(14); the "LFO-CV" vignette of R-loo), forward mode, M steps ahead, on the HIP engine.  The reference
-has no such function.
+*J. Stat. Comput. Simul.* 90(14); the "LFO-CV" vignette of R-loo), forward or backward mode, M steps ahead, on the HIP engine.  The
+reference has no such function.
 
 The observations 0 .. N-1 are in time order.  ``L`` of them come before the first prediction and ``M`` is the horizon: step
 ``t = L .. N-M`` conditions on observations ``[0, t)`` and predicts ``[t, t+M)``,
@@ -17,8 +17,17 @@ the observation axis, the weights pass, the predict kernel, block by block, so t
 host reads one scalar, the first step above the threshold.  The steps beyond it are discarded: a pass costs milliseconds, a refit
 minutes.
 
-Out of scope: backward and combined modes, SIS / TIS, sharding across GPUs, ``loo_compare`` on LFO results, running the refits,
-per-step r_eff estimation (``reff`` is one number per fit).
+``mode="backward"`` is the algorithm as the paper states it.  ``data`` is then the fit to ALL N observations -- the one every user
+already has -- and the walk goes DOWN from ``t = N-M`` to ``L``: a fit that saw the first ``last`` observations serves the steps
+``t <= last`` with the log ratios ``-sum_{r=t}^{last-1} ll[r]``, which remove from the posterior what the step must not have seen.
+Rows ``r >= last`` of a fit's log-likelihood are the conditional terms ``log p(y_r | y_<r, theta)``, which the caller supplies.
+With the full fit step ``N-M`` has already removed M observations, so it may itself ask for a refit.  When k exceeds the threshold at
+step t the model is refitted to the first t observations (``refit(t)``, the same contract), that step is exact, and the walk goes on
+below it.  ``refits`` is in call order, hence descending.  A posterior built on more data moves less per removed observation, so
+this mode usually refits less often, and it needs no extra fit to get started.
+
+Out of scope: a combined mode (the paper defines forward and backward PSIS-LFO-CV and no algorithm that mixes them), SIS / TIS,
+sharding across GPUs, ``loo_compare`` on LFO results, running the refits, per-step r_eff estimation (``reff`` is one number per fit).
 """
 
 import warnings
@@ -106,7 +115,49 @@ def _walk(mat, reff, L, M, refit, k_threshold, var_name):
     return elpd, k, refits, n_replaced, n_first
 
 
-def _result(mat, reff, L, M, refit, k_threshold, scale, pointwise, method, var_name, wrap=None):
+def _walk_backward(mat, reff, L, M, refit, k_threshold, var_name):
+    """The host loop of backward mode, downward from t = N-M: the same five values as ``_walk`` (``refits`` in call order)."""
+    N, n_first = int(mat.shape[0]), int(mat.shape[1])
+    n_total = N - M - L + 1
+    elpd, k = np.empty(n_total), np.empty(n_total)
+    refits, n_replaced = [], 0
+    last, t0 = N, N - M  # the observations the current fit saw; the step its pass begins at
+    while True:
+        S = int(mat.shape[1])
+        tail = tail_count_for(S, reff)
+        if tail + 1 > S:
+            raise IndexError(f"index {-tail - 1} is out of bounds for axis 0 with size {S}")
+        n_steps = t0 - L + 1
+        dev = mat.device.index if _is_torch_tensor(mat) else None
+        res = get_engine(dev).lfo(mat, last, n_steps, M, tail, k_threshold, mode="backward")
+        take = n_steps if refit is None else int(_host(res["first_high"]).reshape(-1)[0])
+        trigger = k[t0 - L] if refits else 0.0  # (the k that asked for this fit, recorded for its first step)
+        lo = t0 - L - take + 1  # step j of the pass is t0 - j: the taken ones fill [lo, t0 - L], reversed
+        elpd[lo:t0 - L + 1] = _host(res["elpd_i"][:take])[::-1]
+        k[lo:t0 - L + 1] = _host(res["diag"][:take])[::-1]
+        if refits:
+            k[t0 - L] = trigger
+        n_replaced += int(_host(res["n_replaced"]).reshape(-1)[0])
+        if take == n_steps:
+            break
+        t0 -= take
+        k[t0 - L] = float(_host(res["diag"][take:take + 1])[0])
+        out = refit(t0)
+        new_reff = reff
+        if isinstance(out, tuple):
+            out, new_reff = out
+        mat = _time_matrix(out, var_name)
+        reff = float(new_reff)
+        if int(mat.shape[0]) != N:
+            raise ValueError(f"refit({t0}) returned a log-likelihood of {int(mat.shape[0])} observations, expected all {N}")
+        refits.append(t0)
+        last = t0
+    return elpd, k, refits, n_replaced, n_first
+
+
+def _result(mat, reff, L, M, refit, k_threshold, scale, pointwise, method, var_name, wrap=None, mode="forward"):
+    if mode not in ("forward", "backward"):
+        raise ValueError(f"mode must be 'forward' or 'backward', got {mode!r}")
     N = int(mat.shape[0])
     _check(N, L, M, method)
     L, M = int(L), int(M)
@@ -117,7 +168,8 @@ def _result(mat, reff, L, M, refit, k_threshold, scale, pointwise, method, var_n
         raise ValueError("k_threshold is NaN")
     scale, scale_value = _scale_value(scale)
     pointwise = rcParams["stats.ic_pointwise"] if pointwise is None else pointwise
-    elpd, k, refits, n_replaced, n_samples = _walk(mat, float(reff), L, M, refit, k_threshold, var_name)
+    walk = _walk if mode == "forward" else _walk_backward
+    elpd, k, refits, n_replaced, n_samples = walk(mat, float(reff), L, M, refit, k_threshold, var_name)
     warn = False
     if n_replaced > 0:  # loo.py:218-227
         warnings.warn("NaN values detected in log-likelihood. These will be ignored in the LOO calculation.", UserWarning, stacklevel=3)
@@ -150,10 +202,12 @@ def _result(mat, reff, L, M, refit, k_threshold, scale, pointwise, method, var_n
     index.append("good_k")
     out = ELPDData(data=data, index=index)
     out.method = "psis"
+    object.__setattr__(out, "lfo_mode", mode)  # (a plain attribute: not a key of the result, whose index is the same in both modes)
     return out
 
 
-def loo_lfo_from_matrix(log_likelihood, L, M=1, refit=None, k_threshold=0.7, reff=1.0, scale=None, pointwise=False, method="psis"):
+def loo_lfo_from_matrix(log_likelihood, L, M=1, refit=None, k_threshold=0.7, reff=1.0, scale=None, pointwise=False, method="psis",
+                        mode="forward"):
     """PSIS leave-future-out CV from an ``(N, S)`` log-likelihood matrix with time along the rows: a NumPy array or a torch CUDA
     tensor (read in place with the draws or the observations contiguous, so a ``.T`` view of an ``(S, N)`` buffer is not copied).
 
@@ -167,20 +221,25 @@ def loo_lfo_from_matrix(log_likelihood, L, M=1, refit=None, k_threshold=0.7, ref
     Returns an ``ELPDData``: ``elpd_lfo``, ``se`` (``sqrt(n_steps var)``), ``n_samples`` (of the first fit), ``n_data_points`` (the
     number of steps), ``warning``, ``scale``, ``L``, ``M``, ``k_threshold``, ``n_refits``, ``refits`` (the steps t at which a refit
     happened; the k recorded there is the one that asked for it), ``good_k``; with ``pointwise=True`` also ``lfo_i`` and
-    ``pareto_k``, length N and indexed by t (NaN where there is no step)."""
+    ``pareto_k``, length N and indexed by t (NaN where there is no step).  The attribute ``lfo_mode`` is the mode.
+
+    ``mode="backward"``: ``log_likelihood`` is that of the fit to ALL N observations; the walk goes down from ``t = N-M`` to ``L``,
+    ``refit(t)`` is called at the first step (from above) whose k exceeds the threshold, and ``refits`` is descending (see the
+    module's text)."""
     if len(log_likelihood.shape) != 2:
         raise ValueError("log_likelihood must be a 2-D (n_obs, n_draws) matrix")
-    return _result(_time_matrix(log_likelihood, None), reff, L, M, refit, k_threshold, scale, pointwise, method, None)
+    return _result(_time_matrix(log_likelihood, None), reff, L, M, refit, k_threshold, scale, pointwise, method, None, mode=mode)
 
 
-def loo_lfo(data, L, M=1, refit=None, var_name=None, k_threshold=0.7, reff=None, scale=None, pointwise=None, method="psis"):
+def loo_lfo(data, L, M=1, refit=None, var_name=None, k_threshold=0.7, reff=None, scale=None, pointwise=None, method="psis",
+            mode="forward"):
     """PSIS leave-future-out CV of a time series model (see :func:`loo_lfo_from_matrix`).
 
     ``data``: the fit to the first ``L`` observations with the log-likelihood of all N -- InferenceData (with ArviZ), a dict of
     groups, or a ``(chain, draw, N)`` array; more than one observation dimension raises ``ValueError`` (time is one axis).
     ``refit(n_train)`` returns the same kind of object for a fit to the first ``n_train`` observations (or an ``(N, S)`` matrix),
     alone or as ``(log_likelihood, reff)``; without a ``reff`` of its own a refit keeps the current one.  ``reff=None`` estimates
-    the relative efficiency of the first fit as ``loo()`` does."""
+    the relative efficiency of the first fit as ``loo()`` does.  ``mode="backward"``: ``data`` is the fit to ALL N observations."""
     idata = to_inference_data(data)
     log_likelihood = get_log_likelihood(idata, var_name=var_name)
     matrix, obs_shape, obs_dims, coords = stack_samples(log_likelihood)
@@ -191,4 +250,4 @@ def loo_lfo(data, L, M=1, refit=None, var_name=None, k_threshold=0.7, reff=None,
 
         reff = _relative_efficiency(idata, matrix.shape[-1])
     return _result(matrix, reff, L, M, refit, k_threshold, scale, pointwise, method, var_name,
-                   wrap=lambda v, name: wrap_obs(v, obs_shape, obs_dims, coords, name))
+                   wrap=lambda v, name: wrap_obs(v, obs_shape, obs_dims, coords, name), mode=mode)

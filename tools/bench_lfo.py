@@ -2,7 +2,7 @@
 """Secondary benchmark: one pass of PSIS leave-future-out CV (Engine.lfo) on a device-resident matrix.
 
     python tools/bench_lfo.py [--obs N] [--draws S] [--dtype f64|f32] [--layout draws|obs] [--horizon M] [--first L]
-                              [--steps K] [--warmup W]
+                              [--steps K] [--warmup W] [--mode forward|backward]
 
 One step = Engine.lfo over all the steps first .. N - M of one fit: per block of steps the prefix-sum kernels, the weights pass and
 the predict kernel, then the first-above-threshold reduction (pla_lfo).  Reported, each as the MEDIAN wall time of --steps
@@ -17,6 +17,12 @@ are timed in rounds, one call of each per round):
                         rows, importance_weights, a window sum of the next M rows, torch.logsumexp twice, the first k above the
                         threshold
   call_block_64mb       the same call in a fresh process with PLA_INGEST_BLOCK_MB=64 (the variable is read once per process)
+--mode backward times the backward pass (Engine.lfo(mode="backward") from the fit to all N observations, the same N - M - first + 1
+steps walked downward) IN THE SAME RUN as the forward call at the same shape, which moves the same bytes, and as its own yardstick:
+  call_backward         the whole backward call at the default block size
+  call_forward          the forward call over the same steps
+  torch_route_backward  the same torch route on the flipped rows: flip, cumsum, negate, importance_weights, a window sum,
+                        torch.logsumexp twice, the first k above the threshold
 One JSON line."""
 import argparse
 import json
@@ -47,6 +53,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--call-only", action="store_true", help="time the call alone (the child run at another block size)")
+    ap.add_argument("--mode", choices=["forward", "backward"], default="forward")
     args = ap.parse_args()
 
     import torch
@@ -81,6 +88,9 @@ def main():
         above = torch.nonzero(k > thr)
         high = int(above[0]) + 1 if above.numel() else n_steps
         return elpd, k, high
+
+    if args.mode == "backward":
+        return backward(args, eng, ll, tail, thr)
 
     variants = {"call": lambda: eng.lfo(ll, first, n_steps, M, tail, thr)}
     if not args.call_only:
@@ -140,6 +150,67 @@ def main():
         stats["call_block_64mb"] = small["spread_wall_ms"]["call"]
         record["env_call_block_64mb"] = small["env"]
     print(json.dumps(record))
+
+
+def backward(args, eng, ll, tail, thr):
+    import torch
+
+    from pyloo_amd._capi import env_overrides
+
+    N, S, M, first = args.obs, args.draws, args.horizon, args.first
+    n_steps = N - first - M + 1  # t = N - M down to first
+    esz = 8 if args.dtype == "f64" else 4
+
+    def torch_route():
+        cs = torch.cumsum(torch.flip(ll[first:], (0,)).double(), 0)  # cs[i] = ll[N - 1] + ... + ll[N - 1 - i]
+        lr = -cs[M - 1:M - 1 + n_steps]                                  # step j = N - M - j removes rows N - M - j .. N - 1
+        lw, k = eng.importance_weights(lr, tail, "psis")
+        f = ll[first:first + n_steps].double()
+        for m in range(1, M):
+            f = f + ll[first + m:first + m + n_steps]
+        f = torch.flip(f, (0,))
+        elpd = torch.logsumexp(lw + f, 1) - torch.logsumexp(lw, 1)
+        above = torch.nonzero(k > thr)
+        high = int(above[0]) if above.numel() else n_steps
+        return elpd, k, high
+
+    variants = {
+        "call_backward": lambda: eng.lfo(ll, N, n_steps, M, tail, thr, mode="backward"),
+        "call_forward": lambda: eng.lfo(ll, first, n_steps, M, tail, thr),
+        "torch_route_backward": torch_route,
+    }
+    out, kernels = {}, {}
+    for name, fn in variants.items():
+        for _ in range(args.warmup):
+            out[name] = fn()
+        kernels[name] = eng.last_kernels()
+    torch.cuda.synchronize()
+    times = {name: [] for name in variants}
+    for _ in range(args.steps):
+        for name, fn in variants.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    stats = {name: spread(ts) for name, ts in times.items()}
+    med = {name: st["median"] for name, st in stats.items()}
+    res = out["call_backward"]
+    elpd_t, k_t, high_t = out["torch_route_backward"]
+    both = torch.isfinite(res["diag"]) & torch.isfinite(k_t)
+    moved = (2.0 + M) * n_steps * S * esz + 4.0 * n_steps * S * 8 + (2.0 * n_steps * S * esz if args.layout == "obs" else 0.0)
+    print(json.dumps({
+        "metric": "lfo_backward_ms_per_pass", "value": med["call_backward"], "unit": "ms", "higher_is_better": False, "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "dtype": args.dtype,
+        "config": {"workload": f"Engine.lfo(mode='backward'), synthetic {args.dtype} N={N}, S={S}, {args.layout} contiguous, last={N}, "
+                               f"horizon={M}, {n_steps} steps down to t={first}, device-resident, tail count {tail}"},
+        "median_wall_ms": med, "spread_wall_ms": stats, "kernels": kernels, "env": env_overrides(),
+        "bytes_moved": moved, "call_bytes_per_second": moved / (med["call_backward"] * 1e-3),
+        "backward_over_forward": med["call_backward"] / med["call_forward"],
+        "backward_over_torch_route": med["call_backward"] / med["torch_route_backward"],
+        "max_abs_difference": {"elpd_vs_torch_route": float((res["elpd_i"] - elpd_t).abs().nan_to_num(0.0, 0.0, 0.0).max()),
+                               "pareto_k_vs_torch_route": float((res["diag"] - k_t)[both].abs().max()) if bool(both.any()) else 0.0},
+        "first_high": int(res["first_high"].item()), "first_high_torch_route": high_t, "n_replaced": int(res["n_replaced"].item()),
+    }))
 
 
 if __name__ == "__main__":

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_UNITS = ["pla_k_general.hip", "pla_k_wave_f64.hip", "pla_k_wave_f32.hip", "pla_k_chunked_f64.hip", "pla_k_chunked_f32.hip",
                 "pla_k_fit.hip", "pla_k_lwout.hip", "pla_k_waic.hip", "pla_k_col.hip", "pla_k_eloo.hip", "pla_k_group.hip",
                 "pla_k_compare.hip", "pla_k_nonfactor.hip", "pla_k_draws.hip", "pla_k_kfold.hip", "pla_k_mm.hip", "pla_k_mixis.hip",
-                "pla_k_pit.hip", "pla_k_lfo.hip", "pla_k_ess.hip", "pla_k_diag.hip"]
+                "pla_k_pit.hip", "pla_k_lfo.hip", "pla_k_lfo_bw.hip", "pla_k_ess.hip", "pla_k_diag.hip"]
 
 
 def compile_isa(extra=(), out="/tmp/pla_isa.s", units=None):
@@ -70,6 +70,8 @@ def unit_of(pat):
         return ["pla_k_mixis.hip"]
     if pat.startswith("pit_"):
         return ["pla_k_pit.hip"]
+    if pat.startswith("lfo_bw_"):
+        return ["pla_k_lfo_bw.hip"]
     if pat.startswith("lfo_"):
         return ["pla_k_lfo.hip"]
     if pat.startswith("ess_"):
