@@ -573,6 +573,55 @@ int pla_loo_diag_weights(pla_engine *eng, const void *lw, const void *ll, int dt
                          int mem_space, void *stream, double *elpd_i, double *ess_w, double *var_log);
 
 /*
+ * LOO influence (csrc/pla_influence.h): what leaving observation i out does to the posterior of n_quant draw-wise quantities
+ * theta[s, j] -- the Bayesian counterpart of DFBETAS and Cook's distance.  With lw row i of the log weights (of any normalisation),
+ * m = max_s lw_s, e_s = exp(lw_s - m) (a weight of log -inf is 0 and the draw contributes to nothing) and
+ * z_sj = (theta_sj - center_j) / scale_j:
+ *     shift[i, j] = sum_s e_s z_sj / sum_s e_s             the standardised leave-one-out mean shift of quantity j
+ *     m2[i, j]    = sum_s e_s z_sj^2 / sum_s e_s           its second moment (sd ratio = sqrt(max(m2 - shift^2, 0)))
+ *     kl[i]       = sum_s e_s (lw_s - m) / sum e - log(sum e) + log(n_draws)     KL(p(. | y_-i) || p(. | y)) of the weighted draws
+ *     ess_w[i]    = (sum e)^2 / sum e^2
+ * A row whose weights are all NaN or all -inf, or hold a NaN or +inf, gives NaN in all four.  A scale_j that is zero or not finite
+ * is the caller's to reject: the NaN or inf of the division is passed through.  All arithmetic is f64 (an f32 matrix is widened
+ * on load); theta, center and scale are always f64.  The contraction W (n x S) . Z (S x P) runs on the f64 matrix cores; there are
+ * no floating-point atomics and an observation's outputs depend on its own row, theta and n_draws alone -- not on the grid, the
+ * block size (PLA_INGEST_BLOCK_MB), the position of the row, the position of the column or the load mode.
+ *
+ * The argument block carries its own size: set struct_size = sizeof(pla_influence_args); a call with another size is PLA_ERR_ARG.
+ *   engine              the engine (NULL: PLA_ERR_ARG)
+ *   mat, dtype, n_obs, n_draws, stride_obs, stride_draw      the matrix, strides in elements
+ *   kind                PLA_PIT_LOGLIK: mat is the log-likelihood; the pipeline of pla_loo_diag (weights of -ll by method and
+ *                       tail_count, one block of rows at a time), diag receives Pareto k / the ESS and *n_replaced the NaN count.
+ *                       PLA_PIT_LOG_WEIGHTS: mat holds log weights; the kernel alone, device matrices read in place with any
+ *                       positive strides, host matrices (unit stride along the draws) staged in blocks; row_index must be NULL,
+ *                       diag is not written and *n_replaced is 0.
+ *   row_index, n_rows   as pla_loo_diag (PLA_PIT_LOGLIK)
+ *   method, tail_count  as pla_importance_weights (PLA_PIT_LOGLIK)
+ *   theta, n_quant, theta_stride_draw, theta_stride_quant    n_draws x n_quant, 1 <= n_quant <= 1024; device: any positive strides;
+ *                       host: dense, (n_draws, n_quant) or (n_quant, n_draws)
+ *   center, scale       [n_quant]
+ *   mem_space, stream   where EVERY pointer of the block lives; PLA_DEVICE: everything is enqueued on stream
+ *   shift, m2           (m, n_quant) C-contiguous, m = n_rows with a row_index, else n_obs;  kl, ess_w, diag: [m];  n_replaced: one
+ *                       int64.  Each output may be NULL.
+ */
+typedef struct pla_influence_args {
+  int64_t struct_size;
+  pla_engine *engine;
+  const void *mat;
+  int32_t dtype, kind, method, mem_space;
+  int64_t n_obs, n_draws, stride_obs, stride_draw;
+  const int64_t *row_index;
+  int64_t n_rows, tail_count;
+  const double *theta;
+  int64_t n_quant, theta_stride_draw, theta_stride_quant;
+  const double *center, *scale;
+  void *stream;
+  double *shift, *m2, *kl, *ess_w, *diag;
+  int64_t *n_replaced;
+} pla_influence_args;
+int pla_loo_influence(const pla_influence_args *args);
+
+/*
  * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
  * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
  * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):

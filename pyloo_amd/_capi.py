@@ -38,9 +38,28 @@ SYMBOLS = (
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
-    "pla_loo_diag", "pla_loo_diag_weights",
+    "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence",
     "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
+
+
+class InfluenceArgs(C.Structure):
+    """``pla_influence_args`` of include/pyloo_amd.h (``struct_size`` is set on construction)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int64), ("engine", C.c_void_p), ("mat", C.c_void_p),
+        ("dtype", C.c_int32), ("kind", C.c_int32), ("method", C.c_int32), ("mem_space", C.c_int32),
+        ("n_obs", C.c_int64), ("n_draws", C.c_int64), ("stride_obs", C.c_int64), ("stride_draw", C.c_int64),
+        ("row_index", C.c_void_p), ("n_rows", C.c_int64), ("tail_count", C.c_int64),
+        ("theta", C.c_void_p), ("n_quant", C.c_int64), ("theta_stride_draw", C.c_int64), ("theta_stride_quant", C.c_int64),
+        ("center", C.c_void_p), ("scale", C.c_void_p), ("stream", C.c_void_p),
+        ("shift", C.c_void_p), ("m2", C.c_void_p), ("kl", C.c_void_p), ("ess_w", C.c_void_p), ("diag", C.c_void_p),
+        ("n_replaced", C.c_void_p),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(InfluenceArgs)
 
 
 class EngineError(RuntimeError):
@@ -128,6 +147,7 @@ def load_library():
     lib.pla_loo_pit.argtypes = [vp, vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, i64, ci, vp, vp, vp, vp, vp]
     lib.pla_loo_diag.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, i64, ci, vp, vp, vp, vp, vp, vp]
     lib.pla_loo_diag_weights.argtypes = [vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp]
+    lib.pla_loo_influence.argtypes = [C.POINTER(InfluenceArgs)]
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]

@@ -3,7 +3,7 @@
 //   pla_capi_core.hip    engine lifecycle, errors, timing, environment report, quantile table, aggregates; every helper declared here
 //   pla_capi_loo.hip     PSIS-LOO pass, importance weights, WAIC, e_loo, synthetic fills
 //   pla_capi_views.hip   groups, draw gather, k-fold
-//   pla_capi_passes.hip  LOO-PIT, diagnostics, leave-future-out, relative efficiency, Mix-IS
+//   pla_capi_passes.hip  LOO-PIT, diagnostics, influence, leave-future-out, relative efficiency, Mix-IS
 //   pla_capi_models.hip  comparison / stacking / bootstrap, moment matching, non-factorised LOO
 #pragma once
 
@@ -105,6 +105,7 @@ struct pla_engine {
   Buffer d_pit;  // LOO-PIT (pla_pit.h): one block of predictive draws, draws fastest (transposed or staged from the host)
   Buffer d_lfo;  // leave-future-out CV (pla_lfo.h): the carry into a block of steps [n_draws], then the carries of its chunks
   Buffer d_ess;  // relative efficiency (pla_ess.h): a slot of centred draws per workgroup of the long-row route
+  Buffer d_inf;  // LOO influence (pla_influence.h): Z^T of the call, zero padded; behind it theta, center and scale of a host call
 
   // ... the k-fold table's pinned host copy (the upload reads it after the call has returned), two of them used in turn, and the
   // event behind each upload: a call waits for the upload of the call before the previous one before it rewrites that copy

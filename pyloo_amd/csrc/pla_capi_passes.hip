@@ -1,5 +1,5 @@
-// C ABI of libpyloo_amd.so, the block-wise passes beside PSIS-LOO: Mix-IS, LOO-PIT, diagnostics, leave-future-out, relative
-// efficiency.
+// C ABI of libpyloo_amd.so, the block-wise passes beside PSIS-LOO: Mix-IS, LOO-PIT, diagnostics, influence, leave-future-out,
+// relative efficiency.
 #include <functional>
 
 #include "pla_capi.h"
@@ -470,6 +470,188 @@ int pla_loo_diag_weights(pla_engine* eng, const void* lw, const void* ll, int dt
   }
   eng->last_kernels = std::string(route) + " (matrices staged in blocks)";
   return out.finish({elpd_i, ess_w, var_log});
+}
+
+// ---- LOO influence (csrc/pla_influence.h) ----------------------------------------------------------------------------------------
+// Z^T of the call into d_inf once, then pla_loo_diag's pipeline with the influence kernel as the consumer of a block's weights in
+// d_lw (PLA_PIT_LOGLIK), or the kernel alone on the caller's weights: a device matrix in place, a host matrix staged through d_in
+// (PLA_PIT_LOG_WEIGHTS).  Outputs of a host call in d_pw: kl, ess_w and diag [m] each, then shift and m2 of ONE block of rows,
+// (rows, n_quant) each, copied to the caller block by block -- bounded like the staging of the input.
+int pla_loo_influence(const pla_influence_args* a) {
+  if (!a) return fail(PLA_ERR_ARG, "args is NULL");
+  if (a->struct_size != (int64_t)sizeof(pla_influence_args))
+    return fail(PLA_ERR_ARG, "struct_size is %lld, pla_influence_args of this library has %lld bytes", (long long)a->struct_size,
+                (long long)sizeof(pla_influence_args));
+  pla_engine* eng = a->engine;
+  if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
+  const bool loglik = a->kind == PLA_PIT_LOGLIK;
+  if (!loglik && a->kind != PLA_PIT_LOG_WEIGHTS) return fail(PLA_ERR_ARG, "bad kind");
+  const int dtype = a->dtype, mem_space = a->mem_space;
+  const int64_t n_obs = a->n_obs, n_draws = a->n_draws, stride_obs = a->stride_obs, stride_draw = a->stride_draw, P = a->n_quant;
+  int rc;
+  if (loglik) {
+    rc = check_common(eng, a->mat, dtype, n_obs, n_draws, stride_obs, stride_draw, a->method, a->tail_count, mem_space);
+    if (rc) return rc;
+  } else {
+    rc = check_engine_types(eng, dtype, mem_space);
+    if (rc) return rc;
+    if (n_obs < 0) return fail(PLA_ERR_ARG, "n_obs < 0");
+    if (n_obs > 0 && !a->mat) return fail(PLA_ERR_ARG, "the matrix pointer is NULL");
+    if (a->row_index) return fail(PLA_ERR_ARG, "row_index needs PLA_PIT_LOGLIK");
+  }
+  if (int rc0 = check_n_draws(n_draws, 2)) return rc0;
+  if (stride_obs <= 0 || stride_draw <= 0) return fail(PLA_ERR_ARG, "strides must be positive");
+  if (P < 1 || P > pla::kInfMaxQuant) return fail(PLA_ERR_ARG, "n_quant must lie in [1, %d], got %lld", pla::kInfMaxQuant, (long long)P);
+  if (!a->theta || !a->center || !a->scale) return fail(PLA_ERR_ARG, "theta / center / scale is NULL");
+  if (a->theta_stride_draw <= 0 || a->theta_stride_quant <= 0) return fail(PLA_ERR_ARG, "theta strides must be positive");
+  if (a->row_index) {
+    rc = check_rows(a->row_index, a->n_rows, n_obs, mem_space);
+    if (rc) return rc;
+  }
+  const int64_t m = a->row_index ? a->n_rows : n_obs;  // rows of this call
+  const bool host = mem_space == PLA_HOST;
+  const bool in_of = loglik && host_obs_fastest(n_obs, n_draws, stride_obs, stride_draw);
+  if (host && stride_draw != 1 && !in_of)
+    return fail(PLA_ERR_UNSUPPORTED, loglik ? "PLA_HOST matrices need unit stride along the draws, or along the observations"
+                                            : "PLA_HOST log weights need unit stride along the draws");
+  if (host && in_of && a->row_index) return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST row selection needs unit stride along the draws");
+  const bool theta_sp = a->theta_stride_quant == 1 && a->theta_stride_draw == P;
+  const bool theta_ps = a->theta_stride_draw == 1 && (P == 1 || a->theta_stride_quant == n_draws);
+  if (host && !theta_sp && !theta_ps) return fail(PLA_ERR_UNSUPPORTED, "PLA_HOST theta must be dense, (n_draws, n_quant) or (n_quant, n_draws)");
+  PLA_ENGINE_CALL(eng, a->stream);
+  if (m == 0) {
+    if (host && a->n_replaced) *a->n_replaced = 0;
+    if (!host && a->n_replaced) PLA_HIP(hipMemsetAsync(a->n_replaced, 0, sizeof(int64_t), s));
+    return PLA_OK;
+  }
+  const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const int S = (int)n_draws, Pq = (int)P;
+
+  // ---- Z^T, once per call
+  int s_pad, p_pad;
+  pla::influence_pads(S, Pq, &s_pad, &p_pad);
+  const size_t zt_doubles = (size_t)s_pad * (size_t)p_pad, th_doubles = (size_t)n_draws * (size_t)P;
+  rc = eng->d_inf.reserve((zt_doubles + (host ? th_doubles + 2 * (size_t)P : 0)) * sizeof(double));
+  if (rc) return rc;
+  double* zt = eng->d_inf.as<double>();
+  const double *d_theta = a->theta, *d_center = a->center, *d_scale = a->scale;
+  if (host) {
+    double* up = zt + zt_doubles;
+    PLA_HIP(hipMemcpyAsync(up, a->theta, th_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+    PLA_HIP(hipMemcpyAsync(up + th_doubles, a->center, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
+    PLA_HIP(hipMemcpyAsync(up + th_doubles + P, a->scale, (size_t)P * sizeof(double), hipMemcpyHostToDevice, s));
+    d_theta = up;
+    d_center = up + th_doubles;
+    d_scale = up + th_doubles + P;
+  }
+  PLA_HIP(pla::launch_influence_prepare(d_theta, a->theta_stride_draw, a->theta_stride_quant, d_center, d_scale, S, Pq, zt, s));
+
+  // ---- the rows of a block, and for PLA_PIT_LOGLIK its weights pass as pla_importance_weights sets it up
+  pla::RowsParams p{};
+  int64_t rows = staged_chunk_rows(mem_space, true, m, n_draws, esz);
+  if (loglik) {
+    rc = weights_block_setup(eng, a->method, a->tail_count, n_draws, esz, s, &rows, &p);
+    if (rc) return rc;
+  }
+
+  // ---- outputs: the caller's device arrays, or engine memory (shift and m2 of a host call: one block at a time)
+  unsigned long long* d_count = nullptr;
+  double *d_shift = a->shift, *d_m2 = a->m2, *d_kl = a->kl, *d_ess = a->ess_w, *d_diag = loglik ? a->diag : nullptr;
+  HostOutputs out(eng, s);
+  if (host) {
+    d_count = eng->counters + pla::kCounterPitReplaced;
+    rc = out.reserve(1, 3 * m + 2 * rows * P, d_count);
+    if (rc) return rc;
+    d_kl = out.col(0);
+    d_ess = d_kl + m;
+    d_diag = d_ess + m;
+    d_shift = d_diag + m;
+    d_m2 = d_shift + (size_t)rows * (size_t)P;
+  } else {
+    d_count = (unsigned long long*)a->n_replaced;
+    if (d_count) PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+  }
+  // the kernel on one block; a host call's shift and m2 go back to the caller behind it (the caller synchronises before the next block)
+  const auto kernel = [&](const void* lw, int64_t r0, int64_t nr, int64_t so, int64_t sd, char* route, int cap) -> int {
+    const size_t at = host ? 0 : (size_t)r0 * (size_t)P;
+    {
+      TimedLaunch t(eng, s);
+      PLA_HIP(pla::launch_influence(lw, dtype, nr, S, so, sd, zt, Pq, d_shift ? d_shift + at : nullptr, d_m2 ? d_m2 + at : nullptr,
+                                    d_kl ? d_kl + r0 : nullptr, d_ess ? d_ess + r0 : nullptr, s, route, cap));
+    }
+    if (host) {
+      const size_t bytes = (size_t)nr * (size_t)P * sizeof(double);
+      if (a->shift) PLA_HIP(hipMemcpyAsync(a->shift + (size_t)r0 * (size_t)P, d_shift, bytes, hipMemcpyDeviceToHost, s));
+      if (a->m2) PLA_HIP(hipMemcpyAsync(a->m2 + (size_t)r0 * (size_t)P, d_m2, bytes, hipMemcpyDeviceToHost, s));
+    }
+    return PLA_OK;
+  };
+  char route[160];
+  std::string label;
+
+  if (!loglik && !host) {  // the kernel alone, the weights in place
+    rc = kernel(a->mat, 0, n_obs, stride_obs, stride_draw, route, (int)sizeof(route));
+    if (rc) return rc;
+    eng->last_kernels = std::string("influence_prepare_kernel -> ") + route + " (matrix read in place)";
+    return PLA_OK;
+  }
+  if (!loglik) {  // ... staged in blocks
+    rc = eng->d_in.reserve((size_t)rows * (size_t)n_draws * esz);
+    if (rc) return rc;
+    for (int64_t r0 = 0; r0 < n_obs; r0 += rows) {
+      const int64_t nr = n_obs - r0 < rows ? n_obs - r0 : rows;
+      rc = upload_rows(a->mat, nullptr, r0, nr, stride_obs, n_draws, esz, eng->d_in.p, s);
+      if (!rc) rc = kernel(eng->d_in.p, r0, nr, n_draws, 1, route, (int)sizeof(route));
+      if (rc) return rc;
+      PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next block
+    }
+    label = std::string("influence_prepare_kernel, rows copied -> ") + route + " (matrix staged in blocks)";
+  } else {
+    const size_t block_bytes = (size_t)rows * (size_t)n_draws * esz;
+    rc = eng->d_in.reserve(block_bytes);
+    if (rc) return rc;
+    if (host && in_of) {
+      rc = eng->d_slab.reserve(block_bytes);
+      if (rc) return rc;
+    }
+    for (int64_t r0 = 0; r0 < m; r0 += rows) {
+      const int64_t nr = m - r0 < rows ? m - r0 : rows;
+      const char* prep = "";
+      if (!host) {
+        PLA_HIP(pla::launch_diag_prepare(a->mat, dtype, n_obs, stride_obs, stride_draw, a->row_index ? a->row_index + r0 : nullptr, r0, nr, S,
+                                         eng->d_in.p, d_count, s, &prep));
+      } else if (in_of) {  // the (n_draws, nr) slab as it lies, turned on the device
+        rc = upload_slab(a->mat, r0, nr, stride_draw, n_draws, esz, eng->d_slab.p, s);
+        if (rc) return rc;
+        PLA_HIP(pla::launch_diag_prepare(eng->d_slab.p, dtype, nr, 1, nr, nullptr, 0, nr, S, eng->d_in.p, d_count, s, &prep));
+      } else {  // (the weights buffer is free until the weights pass writes it)
+        rc = upload_rows(a->mat, a->row_index, r0, nr, stride_obs, n_draws, esz, eng->d_lw.p, s);
+        if (rc) return rc;
+        PLA_HIP(pla::launch_diag_prepare(eng->d_lw.p, dtype, nr, n_draws, 1, nullptr, 0, nr, S, eng->d_in.p, d_count, s, &prep));
+      }
+      p.in = eng->d_in.p;
+      p.n_obs = nr;
+      p.diag = d_diag ? d_diag + r0 : nullptr;
+      p.lw_out = eng->d_lw.p;
+      PLA_HIP(pla::launch_rows(p, dtype, true, s));
+      rc = kernel(eng->d_lw.p, r0, nr, n_draws, 1, route, (int)sizeof(route));
+      if (rc) return rc;
+      if (r0 == 0)
+        label = std::string("influence_prepare_kernel, ") + prep + " -> " + std::string(pla::last_rows_kernels()) + " -> " + route +
+                (host ? " (matrix staged in blocks)" : " per block of observations");
+      if (host) PLA_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next block
+    }
+  }
+  eng->last_kernels = label;
+  if (!host) return PLA_OK;
+  if (a->kl) PLA_HIP(hipMemcpyAsync(a->kl, d_kl, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (a->ess_w) PLA_HIP(hipMemcpyAsync(a->ess_w, d_ess, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (a->diag && loglik) PLA_HIP(hipMemcpyAsync(a->diag, d_diag, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  unsigned long long h_count = 0;
+  PLA_HIP(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (a->n_replaced) *a->n_replaced = (int64_t)h_count;
+  return PLA_OK;
 }
 
 // ---- leave-future-out CV (csrc/pla_lfo.h) ----------------------------------------------------------------------------------------

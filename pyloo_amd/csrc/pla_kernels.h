@@ -225,6 +225,17 @@ hipError_t launch_diag_prepare(const void* in, int dtype, int64_t n_src, int64_t
 hipError_t launch_diag(const void* lw, const void* x, double sign, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs,
                        int64_t lw_stride_draw, int64_t x_stride_obs, int64_t x_stride_draw, double* elpd, double* ess_w, double* var_log,
                        hipStream_t stream, char* route, int cap);
+// LOO influence (pla_influence.h).  influence_pads: the padded extents of Z^T for n_draws x n_quant.  launch_influence_prepare:
+// zt[p_pad][s_pad] = ((theta - center) / scale)^T, zero padded; theta with any positive strides.  launch_influence: shift / m2
+// (n_obs, n_quant) and kl / ess_w [n_obs] (each may be null) from the log weights with their own strides and zt; route: text for
+// pla_engine_last_kernels.
+constexpr int kInfMaxQuant = 1024;
+void influence_pads(int n_draws, int n_quant, int* s_pad, int* p_pad);
+hipError_t launch_influence_prepare(const double* theta, int64_t stride_draw, int64_t stride_quant, const double* center, const double* scale,
+                                    int n_draws, int n_quant, double* zt, hipStream_t stream);
+hipError_t launch_influence(const void* lw, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs, int64_t lw_stride_draw,
+                            const double* zt, int n_quant, double* shift, double* m2, double* kl, double* ess_w,
+                            hipStream_t stream, char* route, int cap);
 // leave-future-out CV (pla_lfo.h).  launch_lfo_ratios: the log ratios of one block of n_rows steps -- whole chunks of
 // lfo_chunk_rows() steps unless it is the last block -- as a contiguous (n_rows, n_draws) f64 matrix; `in` is the row of the block's
 // first step (draws contiguous), rows j < n_load of the block are read (NaN -> -1e10, counted in `replaced`, may be null); carry:

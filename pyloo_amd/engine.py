@@ -906,6 +906,94 @@ class Engine:
                                              p(out[0]), p(out[1]), p(out[2])))
         return {"elpd_i": out[0], "ess_w": out[1], "var_log": out[2]}
 
+    # ------------------------------------------------------------------ LOO influence
+    def loo_influence(self, mat, theta, center, scale, tail_count=0, method="psis", kind="loglik", rows=None):
+        """(n_obs, n_draws) log-likelihood (``kind="loglik"``) or log weights (``kind="log_weights"``) and the draw-wise quantities
+        ``theta`` (n_draws, P) with their ``center`` and ``scale`` [P] -> ``dict(shift, m2, kl, ess_w, diag, n_replaced)``
+        (``pla_loo_influence``): per observation the standardised leave-one-out mean shift and second moment of every quantity
+        (m, P), the KL divergence of the weighted draws from the unweighted ones and the effective sample size of the weights;
+        ``diag`` is the Pareto k (ESS for SIS / TIS), None for log weights.  ``rows``: optional observation indices
+        (``kind="loglik"``), one output row per index.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out,
+        nothing synchronised when ``theta``, ``center`` and ``scale`` are device-resident too (host arrays beside a CUDA matrix are
+        uploaded with a synchronous copy first).  ``theta`` is taken as f64 with its own strides, a ``.T`` view included."""
+        mcode = METHOD_CODES[method]
+        if kind not in ("loglik", "log_weights"):
+            raise ValueError(f"kind must be 'loglik' or 'log_weights', got {kind!r}")
+        loglik = kind == "loglik"
+        if rows is not None and not loglik:
+            raise ValueError("rows= needs kind='loglik'")
+        args = _capi.InfluenceArgs(engine=self._h.value, kind=_capi.PLA_PIT_LOGLIK if loglik else _capi.PLA_PIT_LOG_WEIGHTS, method=mcode,
+                                   tail_count=int(tail_count))
+        if _is_torch_tensor(mat):
+            import torch
+
+            if mat.dim() != 2 or not mat.is_cuda:
+                raise ValueError("expected a 2-D CUDA tensor")
+            if mat.dtype not in (torch.float64, torch.float32):
+                raise TypeError(f"unsupported dtype {mat.dtype}")
+            t = self._library_layout(mat) if loglik else (mat if min(mat.stride()) > 0 else mat.contiguous())
+            n, s = t.shape
+            dev = t.device
+            th = torch.as_tensor(theta, device=dev).to(torch.float64)
+            th = th.reshape(-1, 1) if th.dim() == 1 else th
+            if th.dim() != 2 or th.shape[0] != s:
+                raise ValueError(f"theta must be (n_draws, P) with n_draws = {s}, got {tuple(th.shape)}")
+            if min(th.stride()) <= 0:
+                th = th.contiguous()
+            nq = th.shape[1]
+            cv, sv = (torch.as_tensor(v, device=dev).to(torch.float64).reshape(-1).contiguous() for v in (center, scale))
+            if cv.numel() != nq or sv.numel() != nq:
+                raise ValueError(f"center and scale need {nq} values")
+            idx = None if rows is None else self._device_rows(rows, n, dev)
+            m = n if idx is None else idx.numel()
+            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+            out = {"shift": new(m, nq), "m2": new(m, nq), "kl": new(m), "ess_w": new(m), "diag": new(m) if loglik else None,
+                   "n_replaced": torch.zeros(1, dtype=torch.int64, device=dev)}
+            p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+            args.mem_space, args.stream = PLA_DEVICE, self._stream().value
+            args.dtype = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
+            args.stride_obs, args.stride_draw = (t.stride(0) if n > 1 else max(s, 1)), t.stride(1)
+            args.theta_stride_draw, args.theta_stride_quant = th.stride(0), (th.stride(1) if nq > 1 else 1)
+            keep = (t, th, cv, sv, idx)
+        else:
+            t = self._as_2d_host(mat, allow_obs_fastest=loglik and rows is None)
+            n, s = t.shape
+            th = np.asarray(theta, dtype=np.float64)
+            th = th.reshape(-1, 1) if th.ndim == 1 else th
+            if th.ndim != 2 or th.shape[0] != s:
+                raise ValueError(f"theta must be (n_draws, P) with n_draws = {s}, got {th.shape}")
+            nq = th.shape[1]
+            if th.flags.c_contiguous:
+                std, stq = nq, 1
+            elif th.T.flags.c_contiguous:  # a (P, n_draws) array seen through .T
+                std, stq = 1, s
+            else:
+                th, std, stq = np.ascontiguousarray(th), nq, 1
+            cv, sv = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (center, scale))
+            if cv.size != nq or sv.size != nq:
+                raise ValueError(f"center and scale need {nq} values")
+            idx = None if rows is None else self._host_rows(rows, n)
+            m = n if idx is None else idx.size
+            nrep = np.zeros(1, dtype=np.int64)
+            out = {"shift": np.empty((m, nq)), "m2": np.empty((m, nq)), "kl": np.empty(m), "ess_w": np.empty(m),
+                   "diag": np.empty(m) if loglik else None, "n_replaced": nrep}
+            p = lambda x: None if x is None else x.ctypes.data  # noqa: E731
+            args.mem_space, args.stream = PLA_HOST, None
+            args.dtype = dtype_code(t.dtype)
+            args.stride_obs, args.stride_draw = self._host_strides(t)
+            args.theta_stride_draw, args.theta_stride_quant = std, stq
+            keep = (t, th, cv, sv, idx)
+        args.mat, args.n_obs, args.n_draws = p(t), n, s
+        args.row_index, args.n_rows = p(idx), m
+        args.theta, args.n_quant, args.center, args.scale = p(th), nq, p(cv), p(sv)
+        for k in ("shift", "m2", "kl", "ess_w", "diag", "n_replaced"):
+            setattr(args, k, p(out[k]))
+        check(self._lib.pla_loo_influence(C.byref(args)))
+        del keep
+        if not _is_torch_tensor(mat):
+            out["n_replaced"] = int(out["n_replaced"][0])
+        return out
+
     # ------------------------------------------------------------------ leave-future-out CV
     def _lfo_input(self, ll):
         """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None).  A CUDA tensor with the draws or
