@@ -622,6 +622,65 @@ typedef struct pla_influence_args {
 int pla_loo_influence(const pla_influence_args *args);
 
 /*
+ * GLM log-likelihood generator and PSIS-LOO without the matrix (csrc/pla_glm.h).  For a generalised linear model the
+ * (n_obs, n_draws) log-likelihood is a function of the design matrix x (n_obs x n_pred), the coefficient draws beta (n_draws x
+ * n_pred) and at most one auxiliary parameter per draw; this entry writes it block by block, or consumes each block at once.  f64:
+ *     eta[i, s] = sum_p x[i, p] beta[s, p] + offset_i          the sum on the f64 matrix cores, started from zero
+ *     PLA_GLM_LINPRED          eta itself (PLA_GLM_MODE_MATRIX only)
+ *     PLA_GLM_GAUSSIAN         draw_const_s - 0.5 ((y_i - eta) / draw_scale_s)^2      draw_const_s = -0.5 log(2 pi) - log(sigma_s)
+ *     PLA_GLM_BINOMIAL_LOGIT   obs_const_i + y_i eta - trials_i softplus(eta)          softplus(e) = max(e, 0) + log1p(exp(-|e|));
+ *                              obs_const_i = lgamma(n+1) - lgamma(y+1) - lgamma(n-y+1); trials NULL: 1 (Bernoulli), obs_const NULL: 0
+ *     PLA_GLM_POISSON_LOG      obs_const_i + y_i eta - exp(eta)                        obs_const_i = -lgamma(y_i + 1)
+ * The constants are the caller's.  Values that are not finite propagate by IEEE rules; in PLA_GLM_MODE_LOO a NaN log-likelihood is
+ * replaced by -1e10 and counted (the rule of pla_psis_loo's callers).  eta[i, s] and ll[i, s] depend on row i of x, row s of beta,
+ * n_pred and the vectors' entries alone -- not on the grid, the block size (PLA_INGEST_BLOCK_MB), the position of the row or the
+ * draw, a row list, or the layout and strides of x and beta; there are no floating-point atomics.
+ *
+ * The argument block carries its own size: set struct_size = sizeof(pla_glm_args); a call with another size is PLA_ERR_ARG.
+ *   engine              the engine (NULL: PLA_ERR_ARG)
+ *   family, mode        PLA_GLM_*; PLA_GLM_MODE_MATRIX writes the (m, n_draws) values to out (row pitch out_pitch elements, draws
+ *                       fastest; n_draws >= 1), a device buffer in place, a host buffer block by block through engine memory.
+ *                       PLA_GLM_MODE_LOO (not with PLA_GLM_LINPRED; n_draws >= 2): per block of rows the kernel writes into engine
+ *                       memory and the pass of pla_psis_loo runs on the block; diag / loo_i / lppd_i [m] (each may be NULL), agg
+ *                       [PLA_AGG_COUNT] (may be NULL) over all rows from the pointwise vectors, *n_replaced the NaN count.
+ *   method, tail_count, scale_value, good_k      as pla_psis_loo (PLA_GLM_MODE_LOO)
+ *   x, n_obs, n_pred, x_stride_obs, x_stride_pred            1 <= n_pred <= 256; device: any positive strides; host: dense, either
+ *                       orientation
+ *   beta, n_draws, beta_stride_draw, beta_stride_pred        the same
+ *   y, offset, trials, obs_const     [n_obs]; y is needed by every family but PLA_GLM_LINPRED, the other three may be NULL
+ *   draw_scale, draw_const           [n_draws], PLA_GLM_GAUSSIAN only (NULL: PLA_ERR_ARG there)
+ *   row_index, n_rows   optional rows of x (m = n_rows; repeats and any order allowed), else m = n_obs; a device list is clamped
+ *                       into [0, n_obs), a host list out of range is PLA_ERR_ARG
+ *   mem_space, stream   where EVERY pointer of the block lives; PLA_DEVICE: everything is enqueued on stream
+ */
+#define PLA_GLM_LINPRED 0
+#define PLA_GLM_GAUSSIAN 1
+#define PLA_GLM_BINOMIAL_LOGIT 2
+#define PLA_GLM_POISSON_LOG 3
+#define PLA_GLM_MODE_MATRIX 0
+#define PLA_GLM_MODE_LOO 1
+typedef struct pla_glm_args {
+  int64_t struct_size;
+  pla_engine *engine;
+  int32_t family, mode, method, mem_space;
+  void *stream;
+  const double *x;
+  int64_t n_obs, n_pred, x_stride_obs, x_stride_pred;
+  const double *beta;
+  int64_t n_draws, beta_stride_draw, beta_stride_pred;
+  const double *y, *offset, *trials, *obs_const;
+  const double *draw_scale, *draw_const;
+  const int64_t *row_index;
+  int64_t n_rows, tail_count;
+  double scale_value, good_k;
+  double *out;
+  int64_t out_pitch;
+  double *diag, *loo_i, *lppd_i, *agg;
+  int64_t *n_replaced;
+} pla_glm_args;
+int pla_glm(const pla_glm_args *args);
+
+/*
  * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
  * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
  * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):

@@ -38,7 +38,7 @@ SYMBOLS = (
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
-    "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence",
+    "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence", "pla_glm",
     "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
 
@@ -60,6 +60,34 @@ class InfluenceArgs(C.Structure):
     def __init__(self, **kw):
         super().__init__(**kw)
         self.struct_size = C.sizeof(InfluenceArgs)
+
+
+PLA_GLM_LINPRED, PLA_GLM_GAUSSIAN, PLA_GLM_BINOMIAL_LOGIT, PLA_GLM_POISSON_LOG = 0, 1, 2, 3
+PLA_GLM_MODE_MATRIX, PLA_GLM_MODE_LOO = 0, 1
+GLM_MAX_PRED = 256
+
+
+class GlmArgs(C.Structure):
+    """``pla_glm_args`` of include/pyloo_amd.h (``struct_size`` is set on construction)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int64), ("engine", C.c_void_p),
+        ("family", C.c_int32), ("mode", C.c_int32), ("method", C.c_int32), ("mem_space", C.c_int32),
+        ("stream", C.c_void_p),
+        ("x", C.c_void_p), ("n_obs", C.c_int64), ("n_pred", C.c_int64), ("x_stride_obs", C.c_int64), ("x_stride_pred", C.c_int64),
+        ("beta", C.c_void_p), ("n_draws", C.c_int64), ("beta_stride_draw", C.c_int64), ("beta_stride_pred", C.c_int64),
+        ("y", C.c_void_p), ("offset", C.c_void_p), ("trials", C.c_void_p), ("obs_const", C.c_void_p),
+        ("draw_scale", C.c_void_p), ("draw_const", C.c_void_p),
+        ("row_index", C.c_void_p), ("n_rows", C.c_int64), ("tail_count", C.c_int64),
+        ("scale_value", C.c_double), ("good_k", C.c_double),
+        ("out", C.c_void_p), ("out_pitch", C.c_int64),
+        ("diag", C.c_void_p), ("loo_i", C.c_void_p), ("lppd_i", C.c_void_p), ("agg", C.c_void_p),
+        ("n_replaced", C.c_void_p),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GlmArgs)
 
 
 class EngineError(RuntimeError):
@@ -148,6 +176,7 @@ def load_library():
     lib.pla_loo_diag.argtypes = [vp, vp, ci, i64, i64, i64, i64, vp, i64, ci, i64, ci, vp, vp, vp, vp, vp, vp]
     lib.pla_loo_diag_weights.argtypes = [vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp]
     lib.pla_loo_influence.argtypes = [C.POINTER(InfluenceArgs)]
+    lib.pla_glm.argtypes = [C.POINTER(GlmArgs)]
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]

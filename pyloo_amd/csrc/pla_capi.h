@@ -5,6 +5,7 @@
 //   pla_capi_views.hip   groups, draw gather, k-fold
 //   pla_capi_passes.hip  LOO-PIT, diagnostics, influence, leave-future-out, relative efficiency, Mix-IS
 //   pla_capi_models.hip  comparison / stacking / bootstrap, moment matching, non-factorised LOO
+//   pla_capi_glm.hip     GLM log-likelihood generator and its fused PSIS-LOO pass
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,6 +107,8 @@ struct pla_engine {
   Buffer d_lfo;  // leave-future-out CV (pla_lfo.h): the carry into a block of steps [n_draws], then the carries of its chunks
   Buffer d_ess;  // relative efficiency (pla_ess.h): a slot of centred draws per workgroup of the long-row route
   Buffer d_inf;  // LOO influence (pla_influence.h): Z^T of the call, zero padded; behind it theta, center and scale of a host call
+  Buffer d_glm;     // GLM generator (pla_glm.h): the image of beta, zero padded; behind it X, beta, the vectors and rows of a host call
+  Buffer d_glm_ll;  // ... one block of rows of the log-likelihood (the fused LOO pass; the matrix mode of a host call)
 
   // ... the k-fold table's pinned host copy (the upload reads it after the call has returned), two of them used in turn, and the
   // event behind each upload: a call waits for the upload of the call before the previous one before it rewrites that copy

@@ -236,6 +236,29 @@ hipError_t launch_influence_prepare(const double* theta, int64_t stride_draw, in
 hipError_t launch_influence(const void* lw, int dtype, int64_t n_obs, int n_draws, int64_t lw_stride_obs, int64_t lw_stride_draw,
                             const double* zt, int n_quant, double* shift, double* m2, double* kl, double* ess_w,
                             hipStream_t stream, char* route, int cap);
+// GLM log-likelihood generator (pla_glm.h).  glm_pads: the padded extents of the image of beta for n_draws x n_pred.
+// launch_glm_prepare: bimg[s_pad][p_pad] = beta, zero padded, and kGlmImagePad zeros behind it; beta with any positive strides.  launch_glm: the linear predictor or
+// the log-likelihood of n_rows rows -- row_index[0 .. n_rows) of X, or rows r_first .. -- times all draws into out (row pitch in
+// elements, draws fastest); replaced non-null: NaN -> -1e10, counted; route: text for pla_engine_last_kernels.
+constexpr int kGlmMaxPred = 256;
+constexpr int kGlmImagePad = 2;  // doubles behind the image, zero
+struct GlmLaunch {
+  int family;
+  const double* x;
+  int64_t x_stride_obs, x_stride_pred, n_src;
+  const int64_t* row_index;
+  int64_t r_first, n_rows;
+  const double* bimg;
+  int n_pred, n_draws;
+  const double *y, *offset, *trials, *obs_const, *sigma, *draw_const;
+  double* out;
+  int64_t pitch;
+  unsigned long long* replaced;
+};
+void glm_pads(int n_draws, int n_pred, int* s_pad, int* p_pad);
+hipError_t launch_glm_prepare(const double* beta, int64_t stride_draw, int64_t stride_pred, int n_draws, int n_pred, double* bimg,
+                              hipStream_t stream);
+hipError_t launch_glm(const GlmLaunch& g, hipStream_t stream, char* route, int cap);
 // leave-future-out CV (pla_lfo.h).  launch_lfo_ratios: the log ratios of one block of n_rows steps -- whole chunks of
 // lfo_chunk_rows() steps unless it is the last block -- as a contiguous (n_rows, n_draws) f64 matrix; `in` is the row of the block's
 // first step (draws contiguous), rows j < n_load of the block are read (NaN -> -1e10, counted in `replaced`, may be null); carry:

@@ -994,6 +994,108 @@ class Engine:
             out["n_replaced"] = int(out["n_replaced"][0])
         return out
 
+    # ------------------------------------------------------------------ GLM log-likelihood generator
+    def glm(self, X, beta, family, y=None, offset=None, trials=None, obs_const=None, draw_scale=None, draw_const=None, rows=None,
+            mode="matrix", tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True):
+        """The log-likelihood of a generalised linear model from its design matrix ``X`` (n_obs, P), the coefficient draws ``beta``
+        (n_draws, P) and the family (``pla_glm``): ``"linpred"`` (eta itself), ``"gaussian"``, ``"binomial"`` (logit link), ``"poisson"``
+        (log link).  ``y``, ``offset``, ``trials``, ``obs_const`` are [n_obs], ``draw_scale`` and ``draw_const`` [n_draws] (Gaussian);
+        the constants are the caller's (include/pyloo_amd.h).  ``rows``: optional observation indices, one output row per index.
+        ``mode="matrix"`` returns the (m, n_draws) matrix; ``mode="loo"`` consumes it block by block in the PSIS-LOO pass and returns
+        ``dict(diag, loo_i, lppd_i, agg, n_replaced)``.  NumPy ``X`` -> NumPy out; CUDA tensor -> CUDA tensors, everything else is
+        moved to the device of ``X`` first.  ``X`` and ``beta`` are taken as f64 with their own strides, ``.T`` views included."""
+        fam = {"linpred": _capi.PLA_GLM_LINPRED, "gaussian": _capi.PLA_GLM_GAUSSIAN, "binomial": _capi.PLA_GLM_BINOMIAL_LOGIT,
+               "poisson": _capi.PLA_GLM_POISSON_LOG}
+        if family not in fam:
+            raise ValueError(f"family must be one of {sorted(fam)}, got {family!r}")
+        if mode not in ("matrix", "loo"):
+            raise ValueError(f"mode must be 'matrix' or 'loo', got {mode!r}")
+        loo = mode == "loo"
+        args = _capi.GlmArgs(engine=self._h.value, family=fam[family], mode=_capi.PLA_GLM_MODE_LOO if loo else _capi.PLA_GLM_MODE_MATRIX,
+                             method=METHOD_CODES[method], tail_count=int(tail_count), scale_value=float(scale_value), good_k=float(good_k))
+        obs_vecs = {"y": y, "offset": offset, "trials": trials, "obs_const": obs_const}
+        draw_vecs = {"draw_scale": draw_scale, "draw_const": draw_const}
+        tensor = _is_torch_tensor(X)
+        if tensor:
+            import torch
+
+            if X.dim() != 2 or not X.is_cuda:
+                raise ValueError("expected a 2-D CUDA tensor X")
+            dev = X.device
+            xt = X.to(torch.float64)
+            bt = torch.as_tensor(beta, device=dev).to(torch.float64)
+            if bt.dim() != 2 or bt.shape[1] != xt.shape[1]:
+                raise ValueError(f"beta must be (n_draws, P) with P = {xt.shape[1]}, got {tuple(bt.shape)}")
+            xt, bt = (t if min(t.stride()) > 0 else t.contiguous() for t in (xt, bt))
+            n, npred = xt.shape
+            s = bt.shape[0]
+            vec = lambda v, k: None if v is None else torch.as_tensor(v, device=dev).to(torch.float64).reshape(-1).contiguous()  # noqa: E731
+            xs, bs = xt.stride(), bt.stride()
+            idx = None if rows is None else self._device_rows(rows, n, dev)
+            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+            zeros = lambda: torch.zeros(1, dtype=torch.int64, device=dev)  # noqa: E731
+            p = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+            args.mem_space, args.stream = PLA_DEVICE, self._stream().value
+        else:
+            xt = np.asarray(X, dtype=np.float64)
+            bt = np.asarray(beta, dtype=np.float64)
+            if xt.ndim != 2:
+                raise ValueError("expected a 2-D (n_obs, P) array X")
+            if bt.ndim != 2 or bt.shape[1] != xt.shape[1]:
+                raise ValueError(f"beta must be (n_draws, P) with P = {xt.shape[1]}, got {bt.shape}")
+            n, npred = xt.shape
+            s = bt.shape[0]
+
+            def dense(a):  # (rows, P) as it lies, or the .T view of a dense (P, rows) array
+                if a.flags.c_contiguous:
+                    return a, (a.shape[1], 1)
+                if a.T.flags.c_contiguous:
+                    return a, (1, a.shape[0])
+                return np.ascontiguousarray(a), (a.shape[1], 1)
+
+            (xt, xs), (bt, bs) = dense(xt), dense(bt)
+            vec = lambda v, k: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))  # noqa: E731
+            idx = None if rows is None else self._host_rows(rows, n)
+            new = lambda *shape: np.empty(shape)  # noqa: E731
+            zeros = lambda: np.zeros(1, dtype=np.int64)  # noqa: E731
+            p = lambda v: None if v is None else v.ctypes.data  # noqa: E731
+            args.mem_space, args.stream = PLA_HOST, None
+        keep = [xt, bt, idx]
+        for k, v in obs_vecs.items():
+            v = vec(v, k)
+            if v is not None and len(v) != n:
+                raise ValueError(f"{k} needs {n} values, got {len(v)}")
+            keep.append(v)
+            setattr(args, k, p(v))
+        for k, v in draw_vecs.items():
+            v = vec(v, k)
+            if v is not None and len(v) != s:
+                raise ValueError(f"{k} needs {s} values, got {len(v)}")
+            keep.append(v)
+            setattr(args, k, p(v))
+        m = n if idx is None else len(idx)
+        args.x, args.n_obs, args.n_pred = p(xt), n, npred
+        args.x_stride_obs, args.x_stride_pred = max(int(xs[0]), 1), max(int(xs[1]), 1)
+        args.beta, args.n_draws = p(bt), s
+        args.beta_stride_draw, args.beta_stride_pred = max(int(bs[0]), 1), max(int(bs[1]), 1)
+        args.row_index, args.n_rows = p(idx), m
+        if not loo:
+            out = new(m, s)
+            args.out, args.out_pitch = p(out), s
+            check(self._lib.pla_glm(C.byref(args)))
+            del keep
+            return out
+        pw = pointwise or (aggregate and tensor)
+        res = {"diag": new(m) if pw else None, "loo_i": new(m) if pw else None, "lppd_i": new(m) if pw else None,
+               "agg": new(AGG_COUNT) if aggregate else None, "n_replaced": zeros()}
+        for k, v in res.items():
+            setattr(args, k, p(v))
+        check(self._lib.pla_glm(C.byref(args)))
+        del keep
+        if not tensor:
+            res["n_replaced"] = int(res["n_replaced"][0])
+        return res
+
     # ------------------------------------------------------------------ leave-future-out CV
     def _lfo_input(self, ll):
         """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None).  A CUDA tensor with the draws or

@@ -218,6 +218,75 @@ def importance_resample(log_p, log_q, method="psis", seed=None):
     return indices_subset
 
 
+def _estimate_and_pack(est, approx, indices, loo_m, khat, p_loo_m, n_data_points, n_samples, good_k, scale, pointwise):
+    """The survey-sampling estimators, the warnings and the ``ELPDData`` of a subsample (loo_subsample.py:392-586) from the
+    approximation for all observations and the PSIS-LOO values of the sampled ones: shared by ``loo_subsample_from_matrix`` and
+    ``loo_subsample_glm``, which call it directly (the warnings point at their caller)."""
+    if est == "hh_pps":
+        z = compute_sampling_probabilities(approx)[indices.idx]
+        estimates = hansen_hurwitz_estimate(z, indices.m_i, loo_m, n_data_points)
+        p_est = hansen_hurwitz_estimate(z, indices.m_i, p_loo_m, n_data_points)
+    elif est == "srs":
+        estimates = srs_estimate(loo_m, n_data_points)
+        p_est = srs_estimate(p_loo_m, n_data_points)
+    else:
+        estimates = diff_srs_estimate(approx, loo_m, indices.idx)
+        p_est = srs_estimate(p_loo_m, n_data_points)
+
+    se, sub_se = np.sqrt(estimates.hat_v_y), np.sqrt(estimates.v_y_hat)
+    p_loo, p_loo_se, p_loo_sub_se = p_est.y_hat, np.sqrt(p_est.hat_v_y), np.sqrt(p_est.v_y_hat)
+    looic, looic_se, looic_sub_se = -2 * estimates.y_hat, 2 * se, 2 * sub_se
+
+    warn_mg = False
+    if est == "srs":  # loo_subsample.py:451-461 (the branch reads the PSIS diagnostic as if it were an ESS)
+        min_ess = np.min(khat)
+        if min_ess < n_samples * 0.1:
+            warnings.warn(
+                f"Low effective sample size detected (minimum ESS: {min_ess:.1f}). This"
+                " indicates that the importance sampling approximation may be"
+                " unreliable. Consider using PSIS which is more robust to such cases.",
+                UserWarning,
+                stacklevel=4,
+            )
+            warn_mg = True
+    else:
+        max_k = np.nanmax(khat) if not np.all(np.isnan(khat)) else 0
+        if max_k > good_k:
+            warnings.warn(
+                "Estimated shape parameter of Pareto distribution is greater than"
+                f" {good_k:.2f} for {np.sum(khat > good_k)} observations. This indicates that"
+                " importance sampling may be unreliable because the marginal posterior"
+                " and LOO posterior are very different.",
+                UserWarning,
+                stacklevel=4,
+            )
+            warn_mg = True
+
+    loo_full = np.full(n_data_points, np.nan)
+    loo_full[indices.idx] = loo_m
+    seen = loo_full[~np.isnan(loo_full)]
+    if len(seen) > 0 and np.allclose(seen, seen[0]):
+        warnings.warn(
+            "The point-wise LOO is the same with the sum LOO, please double check "
+            "the Observed RV in your model to make sure it returns element-wise logp.",
+            UserWarning,
+            stacklevel=4,
+        )
+
+    head = [("elpd_loo", estimates.y_hat), ("se", se), ("p_loo", p_loo), ("p_loo_se", p_loo_se),
+            ("p_loo_subsampling_se", p_loo_sub_se), ("n_samples", n_samples), ("n_data_points", n_data_points),
+            ("warning", warn_mg)]
+    tail = [("scale", scale), ("good_k", good_k), ("subsampling_SE", sub_se), ("subsample_size", len(indices.idx)),
+            ("looic", looic), ("looic_se", looic_se), ("looic_subsamp_se", looic_sub_se)]
+    if pointwise:  # index order of loo_subsample.py:545-585
+        rows = head + [("loo_i", loo_full)] + tail + [("pareto_k", khat), ("method", "loo_subsample")]
+    else:          # loo_subsample.py:506-541
+        rows = head + tail + [("method", "loo_subsample")]
+    out = ELPDData(data=[v for _, v in rows], index=[k for k, _ in rows])
+    out.method = "loo_subsample"
+    return out, indices, estimates
+
+
 def loo_subsample_from_matrix(log_likelihood, observations=100, loo_approximation="lpd", estimator="diff_srs",
                               loo_approximation_draws=None, reff=1.0, scale=None, pointwise=False, draw_index=None):
     """Subsampled PSIS-LOO from an ``(n_obs, n_draws)`` matrix (NumPy array, or torch CUDA tensor: device-resident, the
@@ -281,69 +350,7 @@ def loo_subsample_from_matrix(log_likelihood, observations=100, loo_approximatio
     khat = _to_host(res["diag"]).astype(np.float64)
     p_loo_m = _to_host(var_m).astype(np.float64)
 
-    if est == "hh_pps":
-        z = compute_sampling_probabilities(approx)[indices.idx]
-        estimates = hansen_hurwitz_estimate(z, indices.m_i, loo_m, n_data_points)
-        p_est = hansen_hurwitz_estimate(z, indices.m_i, p_loo_m, n_data_points)
-    elif est == "srs":
-        estimates = srs_estimate(loo_m, n_data_points)
-        p_est = srs_estimate(p_loo_m, n_data_points)
-    else:
-        estimates = diff_srs_estimate(approx, loo_m, indices.idx)
-        p_est = srs_estimate(p_loo_m, n_data_points)
-
-    se, sub_se = np.sqrt(estimates.hat_v_y), np.sqrt(estimates.v_y_hat)
-    p_loo, p_loo_se, p_loo_sub_se = p_est.y_hat, np.sqrt(p_est.hat_v_y), np.sqrt(p_est.v_y_hat)
-    looic, looic_se, looic_sub_se = -2 * estimates.y_hat, 2 * se, 2 * sub_se
-
-    warn_mg = False
-    if est == "srs":  # loo_subsample.py:451-461 (the branch reads the PSIS diagnostic as if it were an ESS)
-        min_ess = np.min(khat)
-        if min_ess < n_samples * 0.1:
-            warnings.warn(
-                f"Low effective sample size detected (minimum ESS: {min_ess:.1f}). This"
-                " indicates that the importance sampling approximation may be"
-                " unreliable. Consider using PSIS which is more robust to such cases.",
-                UserWarning,
-                stacklevel=3,
-            )
-            warn_mg = True
-    else:
-        max_k = np.nanmax(khat) if not np.all(np.isnan(khat)) else 0
-        if max_k > good_k:
-            warnings.warn(
-                "Estimated shape parameter of Pareto distribution is greater than"
-                f" {good_k:.2f} for {np.sum(khat > good_k)} observations. This indicates that"
-                " importance sampling may be unreliable because the marginal posterior"
-                " and LOO posterior are very different.",
-                UserWarning,
-                stacklevel=3,
-            )
-            warn_mg = True
-
-    loo_full = np.full(n_data_points, np.nan)
-    loo_full[indices.idx] = loo_m
-    seen = loo_full[~np.isnan(loo_full)]
-    if len(seen) > 0 and np.allclose(seen, seen[0]):
-        warnings.warn(
-            "The point-wise LOO is the same with the sum LOO, please double check "
-            "the Observed RV in your model to make sure it returns element-wise logp.",
-            UserWarning,
-            stacklevel=3,
-        )
-
-    head = [("elpd_loo", estimates.y_hat), ("se", se), ("p_loo", p_loo), ("p_loo_se", p_loo_se),
-            ("p_loo_subsampling_se", p_loo_sub_se), ("n_samples", n_samples), ("n_data_points", n_data_points),
-            ("warning", warn_mg)]
-    tail = [("scale", scale), ("good_k", good_k), ("subsampling_SE", sub_se), ("subsample_size", len(indices.idx)),
-            ("looic", looic), ("looic_se", looic_se), ("looic_subsamp_se", looic_sub_se)]
-    if pointwise:  # index order of loo_subsample.py:545-585
-        rows = head + [("loo_i", loo_full)] + tail + [("pareto_k", khat), ("method", "loo_subsample")]
-    else:          # loo_subsample.py:506-541
-        rows = head + tail + [("method", "loo_subsample")]
-    out = ELPDData(data=[v for _, v in rows], index=[k for k, _ in rows])
-    out.method = "loo_subsample"
-    return out, indices, estimates
+    return _estimate_and_pack(est, approx, indices, loo_m, khat, p_loo_m, n_data_points, n_samples, good_k, scale, pointwise)
 
 
 def loo_subsample(data, observations=100, loo_approximation="plpd", estimator="diff_srs", loo_approximation_draws=None,
