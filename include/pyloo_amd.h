@@ -681,6 +681,40 @@ typedef struct pla_glm_args {
 int pla_glm(const pla_glm_args *args);
 
 /*
+ * pla_glm with group-level terms -- multilevel models: varying intercepts and slopes over grouping factors (csrc/pla_glm_terms.h).
+ *     eta[i, s] = ((( acc[i, s] + offset_i ) + z_0[i] u_0[s, g_0[i]] ) + z_1[i] u_1[s, g_1[i]] ) + ...
+ * acc is pla_glm's sum on the matrix cores; every product and every sum is rounded once, in the order of the terms; with z_t NULL
+ * (a varying intercept) the product is not formed.  Reordering the terms reorders the additions and may change the last bit.
+ * Everything else -- families, modes, the NaN rule, row_index, blocks -- is pla_glm's, and so is its rule of order, extended:
+ * eta[i, s] depends on row i of x, row s of beta, the entries i of the vectors and of g_t and z_t, and on u_t[s, g_t[i]], in the
+ * order of the terms; not on the grid, the block size, positions, a row list, strides, the labels of the groups or the memory
+ * space.  n_terms = 0 gives the bits of pla_glm.
+ *
+ * Set struct_size = sizeof(pla_glm_grouped_args) and glm.struct_size = sizeof(pla_glm_args); another size is PLA_ERR_ARG.
+ *   glm                 the argument block of pla_glm, every field as there
+ *   n_terms             0 .. PLA_GLM_MAX_TERMS
+ *   terms[t]            group_index [n_obs] int32 in [0, n_groups): a device index is clamped into the range on load, a host index
+ *                       out of range is PLA_ERR_ARG; z [n_obs] or NULL (1); u (n_draws x n_groups) with strides u_stride_draw /
+ *                       u_stride_group in elements (device: any positive strides; host: dense, either orientation);
+ *                       1 <= n_groups < 2^31.  All of them live where glm.mem_space says.
+ * Engine memory: the image of the group effects, sum_t n_groups_t x n_draws (padded to 16) doubles.
+ */
+#define PLA_GLM_MAX_TERMS 8
+typedef struct pla_glm_term {
+  const int32_t *group_index;
+  const double *z;
+  const double *u;
+  int64_t u_stride_draw, u_stride_group, n_groups;
+} pla_glm_term;
+typedef struct pla_glm_grouped_args {
+  int64_t struct_size;
+  pla_glm_args glm;
+  int64_t n_terms;
+  pla_glm_term terms[PLA_GLM_MAX_TERMS];
+} pla_glm_grouped_args;
+int pla_glm_grouped(const pla_glm_grouped_args *args);
+
+/*
  * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
  * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
  * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):

@@ -38,7 +38,7 @@ SYMBOLS = (
     "pla_mm_moments", "pla_mm_transform", "pla_mm_ratios",
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
-    "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence", "pla_glm",
+    "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence", "pla_glm", "pla_glm_grouped",
     "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
 
@@ -88,6 +88,29 @@ class GlmArgs(C.Structure):
     def __init__(self, **kw):
         super().__init__(**kw)
         self.struct_size = C.sizeof(GlmArgs)
+
+
+GLM_MAX_TERMS = 8
+
+
+class GlmTerm(C.Structure):
+    """``pla_glm_term`` of include/pyloo_amd.h."""
+
+    _fields_ = [
+        ("group_index", C.c_void_p), ("z", C.c_void_p), ("u", C.c_void_p),
+        ("u_stride_draw", C.c_int64), ("u_stride_group", C.c_int64), ("n_groups", C.c_int64),
+    ]
+
+
+class GlmGroupedArgs(C.Structure):
+    """``pla_glm_grouped_args`` of include/pyloo_amd.h: ``glm`` is a ``GlmArgs`` (both ``struct_size`` are set on construction)."""
+
+    _fields_ = [("struct_size", C.c_int64), ("glm", GlmArgs), ("n_terms", C.c_int64), ("terms", GlmTerm * GLM_MAX_TERMS)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GlmGroupedArgs)
+        self.glm.struct_size = C.sizeof(GlmArgs)
 
 
 class EngineError(RuntimeError):
@@ -177,6 +200,7 @@ def load_library():
     lib.pla_loo_diag_weights.argtypes = [vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp]
     lib.pla_loo_influence.argtypes = [C.POINTER(InfluenceArgs)]
     lib.pla_glm.argtypes = [C.POINTER(GlmArgs)]
+    lib.pla_glm_grouped.argtypes = [C.POINTER(GlmGroupedArgs)]
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]

@@ -109,6 +109,7 @@ struct pla_engine {
   Buffer d_inf;  // LOO influence (pla_influence.h): Z^T of the call, zero padded; behind it theta, center and scale of a host call
   Buffer d_glm;     // GLM generator (pla_glm.h): the image of beta, zero padded; behind it X, beta, the vectors and rows of a host call
   Buffer d_glm_ll;  // ... one block of rows of the log-likelihood (the fused LOO pass; the matrix mode of a host call)
+  Buffer d_glm_u;   // ... pla_glm_grouped alone (pla_glm_terms.h): the image of the group effects; behind it the group indices, z and u of a host call
 
   // ... the k-fold table's pinned host copy (the upload reads it after the call has returned), two of them used in turn, and the
   // event behind each upload: a call waits for the upload of the call before the previous one before it rewrites that copy

@@ -1,5 +1,7 @@
 // C ABI of libpyloo_amd.so, the GLM log-likelihood generator (csrc/pla_glm.h): the matrix from the design matrix, the draws and the
 // family -- written out (PLA_GLM_MODE_MATRIX) or consumed block by block by the PSIS-LOO pass (PLA_GLM_MODE_LOO).
+// pla_glm_grouped is the same pass with group-level terms added to the linear predictor (csrc/pla_glm_terms.h); the image of the group
+// effects, d_glm_u, is its buffer alone.
 // Host code only: argument checks, uploads of a PLA_HOST call, kernel launches on the caller's stream.
 #include "pla_capi.h"
 
@@ -23,15 +25,8 @@ int glm_upload(const double* src, size_t n, double** at, const double** out, hip
   return PLA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pla_glm(const pla_glm_args* a) {
-  if (!a) return fail(PLA_ERR_ARG, "args is NULL");
-  if (a->struct_size != (int64_t)sizeof(pla_glm_args))
-    return fail(PLA_ERR_ARG, "struct_size is %lld, pla_glm_args of this library has %lld bytes", (long long)a->struct_size,
-                (long long)sizeof(pla_glm_args));
+// pla_glm (n_terms = 0, terms null) and pla_glm_grouped behind their own checks of the block's size
+int glm_run(const pla_glm_args* a, int64_t n_terms, const pla_glm_term* terms) {
   pla_engine* eng = a->engine;
   if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
   const int family = a->family, mode = a->mode, mem_space = a->mem_space;
@@ -68,9 +63,29 @@ int pla_glm(const pla_glm_args* a) {
     if (rc) return rc;
   }
   const int64_t m = a->row_index ? a->n_rows : n_obs;  // rows of this call
+  const bool host = mem_space == PLA_HOST;
+  // ---- the group-level terms
+  if (n_terms < 0 || n_terms > PLA_GLM_MAX_TERMS)
+    return fail(PLA_ERR_ARG, "n_terms must lie in [0, %d], got %lld", PLA_GLM_MAX_TERMS, (long long)n_terms);
+  for (int64_t t = 0; t < n_terms; ++t) {
+    const pla_glm_term& k = terms[t];
+    if (k.n_groups < 1 || k.n_groups > INT32_MAX)
+      return fail(PLA_ERR_ARG, "term %lld: n_groups must lie in [1, 2^31), got %lld", (long long)t, (long long)k.n_groups);
+    if (!k.u) return fail(PLA_ERR_ARG, "term %lld: u is NULL", (long long)t);
+    if (n_obs > 0 && !k.group_index) return fail(PLA_ERR_ARG, "term %lld: group_index is NULL", (long long)t);
+    if (k.u_stride_draw <= 0 || k.u_stride_group <= 0) return fail(PLA_ERR_ARG, "term %lld: u strides must be positive", (long long)t);
+    if (!host) continue;
+    const bool u_sg = k.u_stride_group == 1 && (n_draws == 1 || k.u_stride_draw == k.n_groups);
+    const bool u_gs = k.u_stride_draw == 1 && (k.n_groups == 1 || k.u_stride_group == n_draws);
+    if (!u_sg && !u_gs)
+      return fail(PLA_ERR_UNSUPPORTED, "term %lld: PLA_HOST u must be dense, (n_draws, n_groups) or (n_groups, n_draws)", (long long)t);
+    for (int64_t i = 0; i < n_obs; ++i)
+      if (k.group_index[i] < 0 || k.group_index[i] >= k.n_groups)
+        return fail(PLA_ERR_ARG, "term %lld: group_index[%lld] = %d is outside [0, %lld)", (long long)t, (long long)i, (int)k.group_index[i],
+                    (long long)k.n_groups);
+  }
   if (!loo && m > 0 && !a->out) return fail(PLA_ERR_ARG, "out is NULL");
   if (!loo && m > 1 && a->out_pitch < n_draws) return fail(PLA_ERR_ARG, "out_pitch %lld is less than n_draws", (long long)a->out_pitch);
-  const bool host = mem_space == PLA_HOST;
   if (host) {
     const bool x_np = a->x_stride_pred == 1 && (n_obs <= 1 || a->x_stride_obs == P);
     const bool x_pn = a->x_stride_obs == 1 && (P == 1 || a->x_stride_pred == n_obs);
@@ -114,6 +129,39 @@ int pla_glm(const pla_glm_args* a) {
   }
   PLA_HIP(pla::launch_glm_prepare(in.beta, a->beta_stride_draw, a->beta_stride_pred, S, Pp, bimg, s));
 
+  // ---- the image of the group effects once per call (d_glm_u); behind it the indices, z and u of a host call
+  pla::GlmTerms gt{};
+  gt.n_terms = (int)n_terms;
+  if (n_terms > 0) {
+    size_t up_u = 0;  // in 8-byte slots; an int32 index list takes (n_obs + 1) / 2 of them
+    const size_t idx_slots = ((size_t)n_obs + 1) / 2;
+    for (int t = 0; t < gt.n_terms; ++t) {
+      gt.n_groups[t] = (int)terms[t].n_groups;
+      gt.u[t] = terms[t].u;
+      gt.u_stride_draw[t] = terms[t].u_stride_draw;
+      gt.u_stride_group[t] = terms[t].u_stride_group;
+      gt.group[t] = terms[t].group_index;
+      gt.z[t] = terms[t].z;
+      if (host) up_u += idx_slots + (terms[t].z ? (size_t)n_obs : 0) + (size_t)terms[t].n_groups * (size_t)n_draws;
+    }
+    const size_t uimg_n = (size_t)pla::glm_terms_image_size(gt, S);
+    rc = eng->d_glm_u.reserve((uimg_n + up_u) * sizeof(double));
+    if (rc) return rc;
+    double* uimg = eng->d_glm_u.as<double>();
+    if (host) {
+      double* at = uimg + uimg_n;
+      for (int t = 0; t < gt.n_terms; ++t) {
+        PLA_HIP(hipMemcpyAsync(at, terms[t].group_index, (size_t)n_obs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        gt.group[t] = reinterpret_cast<const int32_t*>(at);
+        at += idx_slots;
+        if ((rc = glm_upload(terms[t].z, (size_t)n_obs, &at, &gt.z[t], s))) return rc;
+        if ((rc = glm_upload(terms[t].u, (size_t)terms[t].n_groups * (size_t)n_draws, &at, &gt.u[t], s))) return rc;
+      }
+    }
+    PLA_HIP(pla::launch_glm_terms_prepare(&gt, S, uimg, s));
+  }
+  const std::string prepared = n_terms > 0 ? "glm_prepare_kernel -> glm_terms_prepare_kernel -> " : "glm_prepare_kernel -> ";
+
   pla::GlmLaunch g{};
   g.family = family;
   g.x = in.x;
@@ -138,7 +186,7 @@ int pla_glm(const pla_glm_args* a) {
     g.pitch = pitch;
     g.replaced = count;
     TimedLaunch t(eng, s);
-    PLA_HIP(pla::launch_glm(g, s, route, cap));
+    PLA_HIP(pla::launch_glm_terms(g, gt, s, route, cap));
     return PLA_OK;
   };
   char route[160];
@@ -147,7 +195,7 @@ int pla_glm(const pla_glm_args* a) {
     if (!host) {  // written in place
       rc = block(0, m, a->out, m > 1 ? a->out_pitch : n_draws, nullptr, route, (int)sizeof(route));
       if (rc) return rc;
-      eng->last_kernels = std::string("glm_prepare_kernel -> ") + route + " (matrix written in place)";
+      eng->last_kernels = prepared + route + " (matrix written in place)";
       return PLA_OK;
     }
     const int64_t rows = staged_chunk_rows(mem_space, false, m, n_draws, sizeof(double));
@@ -162,7 +210,7 @@ int pla_glm(const pla_glm_args* a) {
                                hipMemcpyDeviceToHost, s));
       PLA_HIP(hipStreamSynchronize(s));  // the block buffer is reused by the next block
     }
-    eng->last_kernels = std::string("glm_prepare_kernel -> ") + route + " (matrix copied back in blocks)";
+    eng->last_kernels = prepared + route + " (matrix copied back in blocks)";
     return PLA_OK;
   }
 
@@ -204,7 +252,7 @@ int pla_glm(const pla_glm_args* a) {
     rc = psis_loo_run(eng, eng->d_glm_ll.p, PLA_F64, nr, nullptr, nr, n_draws, n_draws, 1, a->method, a->tail_count, a->scale_value,
                       a->good_k, PLA_DEVICE, a->stream, dd ? dd + r0 : nullptr, dl ? dl + r0 : nullptr, dp ? dp + r0 : nullptr, nullptr);
     if (rc) return rc;
-    if (r0 == 0) label = std::string("glm_prepare_kernel -> ") + route + " -> " + eng->last_kernels + " per block of observations";
+    if (r0 == 0) label = prepared + route + " -> " + eng->last_kernels + " per block of observations";
   }
   eng->last_kernels = label;
   // the aggregates once, over all rows, from the pointwise vectors
@@ -222,6 +270,29 @@ int pla_glm(const pla_glm_args* a) {
   PLA_HIP(hipStreamSynchronize(s));
   if (a->n_replaced) *a->n_replaced = (int64_t)h;
   return PLA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pla_glm(const pla_glm_args* a) {
+  if (!a) return fail(PLA_ERR_ARG, "args is NULL");
+  if (a->struct_size != (int64_t)sizeof(pla_glm_args))
+    return fail(PLA_ERR_ARG, "struct_size is %lld, pla_glm_args of this library has %lld bytes", (long long)a->struct_size,
+                (long long)sizeof(pla_glm_args));
+  return glm_run(a, 0, nullptr);
+}
+
+int pla_glm_grouped(const pla_glm_grouped_args* a) {
+  if (!a) return fail(PLA_ERR_ARG, "args is NULL");
+  if (a->struct_size != (int64_t)sizeof(pla_glm_grouped_args))
+    return fail(PLA_ERR_ARG, "struct_size is %lld, pla_glm_grouped_args of this library has %lld bytes", (long long)a->struct_size,
+                (long long)sizeof(pla_glm_grouped_args));
+  if (a->glm.struct_size != (int64_t)sizeof(pla_glm_args))
+    return fail(PLA_ERR_ARG, "glm.struct_size is %lld, pla_glm_args of this library has %lld bytes", (long long)a->glm.struct_size,
+                (long long)sizeof(pla_glm_args));
+  return glm_run(&a->glm, a->n_terms, a->terms);
 }
 
 }  // extern "C"

@@ -70,6 +70,10 @@ struct GlmParams {
   int n_strips, strip_tiles;     // a wavefront's strip: strip_tiles tiles of draws; n_strips strips cover s_pad
 };
 
+// the kernel's parameters of a launch and its grid (pla_k_glm.hip; shared with the flavour with group-level terms, pla_glm_terms.h)
+unsigned glm_fill_params(const GlmLaunch& g, GlmParams* out);
+
+#ifndef PLA_GLM_SHARED_ONLY  // (pla_k_glm_terms.hip takes the shared parts; this kernel is pla_k_glm.hip's)
 __global__ __launch_bounds__(256) void glm_prepare_kernel(GlmPrepareParams P) {
   const int64_t total = (int64_t)P.s_pad * P.p_pad + kGlmImagePad;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -80,6 +84,7 @@ __global__ __launch_bounds__(256) void glm_prepare_kernel(GlmPrepareParams P) {
     P.bimg[e] = b;
   }
 }
+#endif
 
 // the source row of row r of the launch, clamped to the block and to X
 __device__ __forceinline__ int64_t glm_source_row(const GlmParams& P, int64_t r) {

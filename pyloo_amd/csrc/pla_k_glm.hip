@@ -48,10 +48,9 @@ static hipError_t launch_glm_family(const GlmParams& p, unsigned grid, hipStream
   return hipSuccess;
 }
 
-hipError_t launch_glm(const GlmLaunch& g, hipStream_t stream, char* route, int cap) {
-  if (route && cap > 0) route[0] = 0;
-  if (g.n_rows <= 0 || g.n_draws <= 0 || g.n_pred <= 0) return hipSuccess;
-  GlmParams p{};
+unsigned glm_fill_params(const GlmLaunch& g, GlmParams* out) {
+  GlmParams& p = *out;
+  p = GlmParams{};
   p.x = g.x;
   p.sx_obs = g.x_stride_obs;
   p.sx_pred = g.x_stride_pred;
@@ -82,7 +81,14 @@ hipError_t launch_glm(const GlmLaunch& g, hipStream_t stream, char* route, int c
   if (strips > n_dtiles) strips = n_dtiles;
   p.strip_tiles = (int)((n_dtiles + strips - 1) / strips);
   p.n_strips = (n_dtiles + p.strip_tiles - 1) / p.strip_tiles;
-  const unsigned grid = glm_grid((row_tiles * p.n_strips + kGlmWaves - 1) / kGlmWaves, (int64_t)1 << 20);
+  return glm_grid((row_tiles * p.n_strips + kGlmWaves - 1) / kGlmWaves, (int64_t)1 << 20);
+}
+
+hipError_t launch_glm(const GlmLaunch& g, hipStream_t stream, char* route, int cap) {
+  if (route && cap > 0) route[0] = 0;
+  if (g.n_rows <= 0 || g.n_draws <= 0 || g.n_pred <= 0) return hipSuccess;
+  GlmParams p;
+  const unsigned grid = glm_fill_params(g, &p);
   hipError_t e;
   const char* name;
   switch (g.family) {

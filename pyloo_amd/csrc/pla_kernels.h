@@ -259,6 +259,24 @@ void glm_pads(int n_draws, int n_pred, int* s_pad, int* p_pad);
 hipError_t launch_glm_prepare(const double* beta, int64_t stride_draw, int64_t stride_pred, int n_draws, int n_pred, double* bimg,
                               hipStream_t stream);
 hipError_t launch_glm(const GlmLaunch& g, hipStream_t stream, char* route, int cap);
+// ... with group-level terms (pla_glm_terms.h): eta += z_t[i] u_t[s, g_t[i]], t = 0 .. n_terms - 1, in that order.
+// launch_glm_terms_prepare: uimg[sum G_t][s_pad], group-major, draws fastest, zero for s >= n_draws; term t starts at row first[t]
+// (filled in here, first[n_terms] the number of rows); u_t with any positive strides.  launch_glm_terms: launch_glm with the terms
+// added to the accumulator registers; group / z are [n_src] (z[t] null: 1), a group index is clamped into [0, n_groups) on load.
+constexpr int kGlmMaxTerms = 8;
+struct GlmTerms {
+  int n_terms;
+  const double* u[kGlmMaxTerms];
+  int64_t u_stride_draw[kGlmMaxTerms], u_stride_group[kGlmMaxTerms];
+  int n_groups[kGlmMaxTerms];
+  const int32_t* group[kGlmMaxTerms];
+  const double* z[kGlmMaxTerms];
+  int64_t first[kGlmMaxTerms + 1];
+  const double* uimg;
+};
+int64_t glm_terms_image_size(const GlmTerms& t, int n_draws);  // doubles
+hipError_t launch_glm_terms_prepare(GlmTerms* t, int n_draws, double* uimg, hipStream_t stream);
+hipError_t launch_glm_terms(const GlmLaunch& g, const GlmTerms& t, hipStream_t stream, char* route, int cap);
 // leave-future-out CV (pla_lfo.h).  launch_lfo_ratios: the log ratios of one block of n_rows steps -- whole chunks of
 // lfo_chunk_rows() steps unless it is the last block -- as a contiguous (n_rows, n_draws) f64 matrix; `in` is the row of the block's
 // first step (draws contiguous), rows j < n_load of the block are read (NaN -> -1e10, counted in `replaced`, may be null); carry:

@@ -996,14 +996,17 @@ class Engine:
 
     # ------------------------------------------------------------------ GLM log-likelihood generator
     def glm(self, X, beta, family, y=None, offset=None, trials=None, obs_const=None, draw_scale=None, draw_const=None, rows=None,
-            mode="matrix", tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True):
+            mode="matrix", tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True, groups=None):
         """The log-likelihood of a generalised linear model from its design matrix ``X`` (n_obs, P), the coefficient draws ``beta``
         (n_draws, P) and the family (``pla_glm``): ``"linpred"`` (eta itself), ``"gaussian"``, ``"binomial"`` (logit link), ``"poisson"``
         (log link).  ``y``, ``offset``, ``trials``, ``obs_const`` are [n_obs], ``draw_scale`` and ``draw_const`` [n_draws] (Gaussian);
         the constants are the caller's (include/pyloo_amd.h).  ``rows``: optional observation indices, one output row per index.
         ``mode="matrix"`` returns the (m, n_draws) matrix; ``mode="loo"`` consumes it block by block in the PSIS-LOO pass and returns
         ``dict(diag, loo_i, lppd_i, agg, n_replaced)``.  NumPy ``X`` -> NumPy out; CUDA tensor -> CUDA tensors, everything else is
-        moved to the device of ``X`` first.  ``X`` and ``beta`` are taken as f64 with their own strides, ``.T`` views included."""
+        moved to the device of ``X`` first.  ``X`` and ``beta`` are taken as f64 with their own strides, ``.T`` views included.
+        ``groups``: group-level terms, a sequence of ``(index, draws)`` or ``(index, draws, z)`` -- ``index`` [n_obs] integers in
+        ``[0, G)``, ``draws`` (n_draws, G) with its own strides, ``z`` [n_obs] or None (1) --, added to the linear predictor in the
+        order given (``pla_glm_grouped``; an empty sequence goes through that entry with no terms, None through ``pla_glm``)."""
         fam = {"linpred": _capi.PLA_GLM_LINPRED, "gaussian": _capi.PLA_GLM_GAUSSIAN, "binomial": _capi.PLA_GLM_BINOMIAL_LOGIT,
                "poisson": _capi.PLA_GLM_POISSON_LOG}
         if family not in fam:
@@ -1079,10 +1082,44 @@ class Engine:
         args.beta, args.n_draws = p(bt), s
         args.beta_stride_draw, args.beta_stride_pred = max(int(bs[0]), 1), max(int(bs[1]), 1)
         args.row_index, args.n_rows = p(idx), m
+        terms = []
+        if groups is not None:
+            if len(groups) > _capi.GLM_MAX_TERMS:
+                raise ValueError(f"at most {_capi.GLM_MAX_TERMS} group-level terms are supported, got {len(groups)}")
+            for t, term in enumerate(groups):
+                gi, u, z = (*term, None)[:3]
+                if tensor:
+                    gi = torch.as_tensor(gi, device=dev).to(torch.int32).reshape(-1).contiguous()
+                    u = torch.as_tensor(u, device=dev).to(torch.float64)
+                    if u.dim() == 2 and min(u.stride()) <= 0:
+                        u = u.contiguous()
+                    us = u.stride() if u.dim() == 2 else None
+                else:
+                    gi = np.ascontiguousarray(np.asarray(gi).reshape(-1), dtype=np.int32)
+                    u = np.asarray(u, dtype=np.float64)
+                    u, us = dense(u) if u.ndim == 2 else (u, None)
+                z = vec(z, "z")
+                if us is None or u.shape[0] != s or u.shape[1] < 1:
+                    raise ValueError(f"draws of term {t} must be (n_draws, G) with n_draws = {s} and G >= 1, got {tuple(u.shape)}")
+                if len(gi) != n or (z is not None and len(z) != n):
+                    raise ValueError(f"index and z of term {t} need {n} values")
+                keep += [gi, u, z]
+                terms.append((p(gi), p(z), p(u), max(int(us[0]), 1), max(int(us[1]), 1), int(u.shape[1])))
+
+        def run():
+            if groups is None:
+                check(self._lib.pla_glm(C.byref(args)))
+                return
+            grouped = _capi.GlmGroupedArgs(n_terms=len(terms))
+            grouped.glm = args
+            for t, (gp, zp, up, sd, sg, ng) in enumerate(terms):
+                grouped.terms[t] = _capi.GlmTerm(group_index=gp, z=zp, u=up, u_stride_draw=sd, u_stride_group=sg, n_groups=ng)
+            check(self._lib.pla_glm_grouped(C.byref(grouped)))
+
         if not loo:
             out = new(m, s)
             args.out, args.out_pitch = p(out), s
-            check(self._lib.pla_glm(C.byref(args)))
+            run()
             del keep
             return out
         pw = pointwise or (aggregate and tensor)
@@ -1090,7 +1127,7 @@ class Engine:
                "agg": new(AGG_COUNT) if aggregate else None, "n_replaced": zeros()}
         for k, v in res.items():
             setattr(args, k, p(v))
-        check(self._lib.pla_glm(C.byref(args)))
+        run()
         del keep
         if not tensor:
             res["n_replaced"] = int(res["n_replaced"][0])

@@ -14,6 +14,12 @@ Families: ``"gaussian"`` (identity link, ``sigma`` per draw), ``"bernoulli"`` an
 link).  NumPy ``X`` -> NumPy results; a torch CUDA ``X`` -> everything is moved to its device and stays there.  The fronts compute
 the per-observation and per-draw constants the kernel is handed (``obs_const``, ``draw_const``): ``scipy.special.gammaln`` /
 ``np.log`` on the host, ``torch.lgamma`` / ``torch.log`` on the device.
+
+Multilevel models: ``groups=`` is a sequence of at most eight group-level terms, ``(index, draws)`` -- a varying intercept -- or
+``(index, draws, z)`` -- a varying slope on the covariate ``z`` [N] --, with ``index`` [N] integers in ``[0, G)`` and ``draws``
+(S, G).  The linear predictor becomes ``((X beta + offset) + z_0 u_0[:, index_0]) + z_1 u_1[:, index_1] + ...``, every product and
+sum rounded once in the order given (``pla_glm_grouped``, csrc/pla_glm_terms.h): another order of the terms is another order of
+additions and may differ in the last bit.  A term over a product of factors takes the joint index, formed by the caller.
 """
 
 import warnings
@@ -31,6 +37,7 @@ __all__ = ["glm_log_lik", "glm_plpd", "loo_glm_from_design", "loo_glm", "loo_sub
 
 FAMILIES = ("gaussian", "bernoulli", "binomial", "poisson")
 MAX_PREDICTORS = 256
+MAX_TERMS = 8
 _ENGINE_FAMILY = {"gaussian": "gaussian", "bernoulli": "binomial", "binomial": "binomial", "poisson": "poisson"}
 _HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
 
@@ -117,6 +124,70 @@ def _prepare(X, y, beta, family, sigma, offset, trials):
     return X, beta, {"y": y, "offset": offset, "trials": trials, "obs_const": obs_const, "draw_scale": sigma, "draw_const": draw_const}
 
 
+def _prepare_groups(groups, X, n_draws):
+    """Every check of the group-level terms, before any engine call: ``[(index, draws, z), ...]`` in the memory space of ``X``, or
+    None when there is no term (``groups`` None or empty: the call without terms)."""
+    if groups is None:
+        return None
+    groups = list(groups)
+    if not groups:
+        return None
+    if len(groups) > MAX_TERMS:
+        raise ValueError(f"at most {MAX_TERMS} group-level terms are supported, got {len(groups)}")
+    n = X.shape[0]
+    tensor = _is_torch_tensor(X)
+    if tensor:
+        import torch
+    out = []
+    for t, term in enumerate(groups):
+        if not isinstance(term, (tuple, list)) or len(term) not in (2, 3):
+            raise ValueError(f"groups[{t}] must be (index, draws) or (index, draws, z)")
+        index, draws, z = (*term, None)[:3]
+        if tensor:
+            index = torch.as_tensor(index, device=X.device).reshape(-1)
+            integer = not (index.is_floating_point() or index.is_complex() or index.dtype == torch.bool)
+            draws = torch.as_tensor(draws, device=X.device).to(torch.float64)
+            z = None if z is None else torch.as_tensor(z, device=X.device).to(torch.float64).reshape(-1)
+            finite, ndim = torch.isfinite, draws.dim()
+        else:
+            index = np.asarray(index).reshape(-1)
+            integer = np.issubdtype(index.dtype, np.integer)
+            draws = np.asarray(draws, dtype=np.float64)
+            z = None if z is None else np.asarray(z, dtype=np.float64).reshape(-1)
+            finite, ndim = np.isfinite, draws.ndim
+        if not integer:
+            raise TypeError(f"groups[{t}]: index must hold integers, got dtype {index.dtype}")
+        if index.shape[0] != n:
+            raise ValueError(f"groups[{t}]: index needs {n} values, one per row of X, got {index.shape[0]}")
+        if ndim != 2 or draws.shape[0] != n_draws:
+            raise ValueError(f"groups[{t}]: draws must be a 2-D (n_draws, G) array with n_draws = {n_draws} rows as beta has, "
+                             f"got shape {tuple(draws.shape)}")
+        g = draws.shape[1]
+        if g == 0:
+            raise ValueError(f"groups[{t}]: draws has no groups (G = 0)")
+        if n > 0:
+            lo, hi = int(index.min()), int(index.max())
+            if lo < 0 or hi >= g:
+                raise ValueError(f"groups[{t}]: index must lie in [0, {g}), got range [{lo}, {hi}]")
+        if z is not None and z.shape[0] != n:
+            raise ValueError(f"groups[{t}]: z needs {n} values, got {z.shape[0]}")
+        for name, a in (("draws", draws), ("z", z)):
+            if a is not None and not _all(finite(a)):
+                raise ValueError(f"groups[{t}]: {name} holds values that are not finite")
+        out.append((index, draws, z))
+    return out
+
+
+def _with_groups(terms):
+    """The keyword the engine is handed: none at all without terms -- the existing call with the existing arguments."""
+    return {} if terms is None else {"groups": terms}
+
+
+def _groups_at(terms, pick):
+    """The terms with ``pick`` applied to the draws of each: the posterior mean, a thinned set of draws."""
+    return None if terms is None else [(index, pick(draws), z) for index, draws, z in terms]
+
+
 def _engine_of(X):
     return get_engine(X.device.index if _is_torch_tensor(X) else None)
 
@@ -127,15 +198,16 @@ def _check_reff(reff):
     return float(reff)
 
 
-def glm_log_lik(X, y, beta, family, sigma=None, offset=None, trials=None, rows=None, linpred=False):
+def glm_log_lik(X, y, beta, family, sigma=None, offset=None, trials=None, rows=None, linpred=False, groups=None):
     """The ``(m, S)`` log-likelihood matrix of a GLM -- of all N rows of ``X``, or of ``rows`` (any order, repeats allowed) -- or,
-    with ``linpred=True``, the posterior linear predictor ``X @ beta.T + offset``.  torch on the device for a CUDA ``X``, NumPy
-    otherwise."""
+    with ``linpred=True``, the posterior linear predictor ``X @ beta.T + offset`` (plus the terms of ``groups``, see the module's
+    text).  torch on the device for a CUDA ``X``, NumPy otherwise."""
     Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    terms = _prepare_groups(groups, Xc, bc.shape[0])
     eng = _engine_of(Xc)
     if linpred:
-        return eng.glm(Xc, bc, "linpred", offset=v["offset"], rows=rows)
-    return eng.glm(Xc, bc, _ENGINE_FAMILY[family], rows=rows, **v)
+        return eng.glm(Xc, bc, "linpred", offset=v["offset"], rows=rows, **_with_groups(terms))
+    return eng.glm(Xc, bc, _ENGINE_FAMILY[family], rows=rows, **v, **_with_groups(terms))
 
 
 def _posterior_mean(beta, v):
@@ -149,24 +221,30 @@ def _posterior_mean(beta, v):
     return b1, v1
 
 
-def glm_plpd(X, y, beta, family, sigma=None, offset=None, trials=None):
-    """``[N]``: the log-likelihood of every observation at the posterior mean of ``beta`` (and of ``sigma``) -- the point log
-    predictive density of Magnusson et al. (2019), the matrix mode with one draw."""
+def _mean_draw(draws):
+    return draws.mean(0).reshape(1, -1)
+
+
+def glm_plpd(X, y, beta, family, sigma=None, offset=None, trials=None, groups=None):
+    """``[N]``: the log-likelihood of every observation at the posterior mean of ``beta`` (of ``sigma``, and of the draws of every
+    term of ``groups``) -- the point log predictive density of Magnusson et al. (2019), the matrix mode with one draw."""
     Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    terms = _prepare_groups(groups, Xc, bc.shape[0])
     b1, v1 = _posterior_mean(bc, v)
-    return _engine_of(Xc).glm(Xc, b1, _ENGINE_FAMILY[family], **v1).reshape(-1)
+    return _engine_of(Xc).glm(Xc, b1, _ENGINE_FAMILY[family], **v1, **_with_groups(_groups_at(terms, _mean_draw))).reshape(-1)
 
 
 def loo_glm_from_design(X, y, beta, family, sigma=None, offset=None, trials=None, reff=1.0, scale=None, method="psis", pointwise=False,
-                        rows=None):
+                        rows=None, groups=None):
     """PSIS-LOO of a GLM from its design matrix ``X`` (N, P), the outcomes ``y`` [N] and the draws ``beta`` (S, P), in one fused
     pass: per block of observations the log-likelihood is generated into a bounded buffer and consumed by the LOO kernels.
     Returns the ``ELPDData`` of ``loo_from_matrix`` on the materialised matrix -- the same keys, warnings and texts.  ``rows``:
-    the pass over these observations only."""
+    the pass over these observations only.  ``groups``: the group-level terms of a multilevel model (the module's text)."""
     method = parse_method(method)
     scale, scale_value = _scale_value(scale)
     reff = _check_reff(reff)
     Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    terms = _prepare_groups(groups, Xc, bc.shape[0])
     n_samples = bc.shape[0]
     if n_samples < 2:
         raise ValueError("PSIS-LOO needs at least two draws")
@@ -175,7 +253,7 @@ def loo_glm_from_design(X, y, beta, family, sigma=None, offset=None, trials=None
     if method == ISMethod.PSIS and M + 1 > n_samples:
         raise IndexError(f"index {-M - 1} is out of bounds for axis 0 with size {n_samples}")
     res = _engine_of(Xc).glm(Xc, bc, _ENGINE_FAMILY[family], rows=rows, mode="loo", tail_count=M, method=method.value,
-                             scale_value=scale_value, good_k=good_k, **v)
+                             scale_value=scale_value, good_k=good_k, **v, **_with_groups(terms))
     if int(res["n_replaced"]) > 0:
         warnings.warn("NaN values detected in log-likelihood. These will be ignored in the LOO calculation.", UserWarning, stacklevel=2)
     agg = _to_host(res["agg"])
@@ -188,10 +266,12 @@ def loo_glm_from_design(X, y, beta, family, sigma=None, offset=None, trials=None
 
 
 def loo_glm(idata, X, y, family, var_names, sigma_name=None, var_name=None, offset=None, trials=None, reff=1.0, scale=None,
-            method="psis", pointwise=False, rows=None):
+            method="psis", pointwise=False, rows=None, group_terms=None):
     """``loo_glm_from_design`` with the draws taken from ``idata``: the columns of ``beta`` are the variables ``var_names`` of the
     ``posterior`` group, each flattened over its own dimensions, in the order given; their count must equal ``X.shape[1]``.
-    ``sigma_name``: the posterior variable that holds the Gaussian scale.  ``y=None`` reads ``observed_data[var_name]``."""
+    ``sigma_name``: the posterior variable that holds the Gaussian scale.  ``y=None`` reads ``observed_data[var_name]``.
+    ``group_terms``: a sequence of ``(name, index)`` or ``(name, index, z)`` -- the posterior variable ``name`` of shape
+    ``(chain, draw, G)`` holds the group effects of the term --, handed on as ``groups`` in the order given."""
     data = to_inference_data(idata)
     beta, names, _ = _posterior_columns(data, var_names)
     if beta.shape[1] != X.shape[1]:
@@ -207,17 +287,27 @@ def loo_glm(idata, X, y, family, var_names, sigma_name=None, var_name=None, offs
             raise ValueError("y=None needs var_name and an observed_data group")
         obs = data.observed_data[var_name]
         y = np.asarray(getattr(obs, "values", obs), dtype=np.float64).reshape(-1)
+    groups = None
+    if group_terms is not None:
+        groups = []
+        for t, term in enumerate(group_terms):
+            if not isinstance(term, (tuple, list)) or len(term) not in (2, 3) or not isinstance(term[0], str):
+                raise ValueError(f"group_terms[{t}] must be (name, index) or (name, index, z)")
+            draws, _, _ = _posterior_columns(data, [term[0]])
+            groups.append((term[1], draws, *term[2:]))
     return loo_glm_from_design(X, y, beta, family, sigma=sigma, offset=offset, trials=trials, reff=reff, scale=scale, method=method,
-                               pointwise=pointwise, rows=rows)
+                               pointwise=pointwise, rows=rows, groups=groups)
 
 
 def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="plpd", estimator="diff_srs",
-                      loo_approximation_draws=None, sigma=None, offset=None, trials=None, reff=1.0, scale=None, pointwise=False):
+                      loo_approximation_draws=None, sigma=None, offset=None, trials=None, reff=1.0, scale=None, pointwise=False,
+                      groups=None):
     """Subsampled PSIS-LOO (Magnusson et al. 2019, 2020) of a GLM without its matrix.  The approximation for ALL observations is
     ``"plpd"`` -- ``glm_plpd``, the log-likelihood at the posterior mean -- or ``"lpd"``, the ``lppd_i`` of a fused pass over
     (thinned) draws; the subsample is drawn by ``subsample_indices``; only the ``m`` sampled rows of the matrix are generated
     (``glm_log_lik(rows=idx)``) and go through PSIS-LOO and the variance over draws.  Estimators, warnings and result layout are
-    those of ``loo_subsample_from_matrix``.  Returns ``(ELPDData, SubsampleIndices, Estimate)``."""
+    those of ``loo_subsample_from_matrix``.  ``groups``: the group-level terms of a multilevel model (the module's text).  Returns
+    ``(ELPDData, SubsampleIndices, Estimate)``."""
     kind = str(loo_approximation).lower()
     if kind not in ("plpd", "lpd"):
         raise ValueError(f"Invalid loo_approximation '{loo_approximation}'. Must be one of: plpd, lpd (of {', '.join(APPROXIMATIONS)})")
@@ -227,6 +317,7 @@ def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="p
     scale, scale_value = _scale_value(scale)
     reff = _check_reff(reff)
     Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    terms = _prepare_groups(groups, Xc, bc.shape[0])
     n_data_points, n_samples = Xc.shape[0], bc.shape[0]
     if isinstance(observations, (int, np.integer)) and not isinstance(observations, bool):
         if observations <= 0 or observations > n_data_points:
@@ -252,9 +343,9 @@ def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="p
     fam = _ENGINE_FAMILY[family]
     if kind == "plpd":
         b1, v1 = _posterior_mean(bc, v)
-        approx = _to_host(eng.glm(Xc, b1, fam, **v1)).reshape(-1).astype(np.float64)
+        approx = _to_host(eng.glm(Xc, b1, fam, **v1, **_with_groups(_groups_at(terms, _mean_draw)))).reshape(-1).astype(np.float64)
     else:
-        bt, vt = bc, v
+        bt, vt, tt = bc, v, terms
         if loo_approximation_draws is not None:  # approximations/base.py:60-102: evenly spaced draws
             cols = np.linspace(0, n_samples - 1, loo_approximation_draws, dtype=int)
             if _is_torch_tensor(bc):
@@ -265,13 +356,14 @@ def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="p
             vt = dict(v)
             for k in ("draw_scale", "draw_const"):
                 vt[k] = None if v[k] is None else v[k][cols]
-        approx = _to_host(eng.glm(Xc, bt, fam, mode="loo", method="sis", aggregate=False, **vt)["lppd_i"]).astype(np.float64)
+            tt = _groups_at(terms, lambda draws: draws[cols])
+        approx = _to_host(eng.glm(Xc, bt, fam, mode="loo", method="sis", aggregate=False, **vt, **_with_groups(tt))["lppd_i"]).astype(np.float64)
     if isinstance(observations, np.ndarray):
         indices = SubsampleIndices(idx=observations, m_i=np.ones_like(observations))
     else:
         indices = subsample_indices(est, approx, int(observations))
 
-    sub = eng.glm(Xc, bc, fam, rows=indices.idx, **v)  # the m sampled rows, draws fastest
+    sub = eng.glm(Xc, bc, fam, rows=indices.idx, **v, **_with_groups(terms))  # the m sampled rows, draws fastest
     res = eng.psis_loo(sub, M, ISMethod.PSIS.value, scale_value, good_k, aggregate=False)
     var_m = eng.waic(sub, 1.0, aggregate=False)["var_i"]
     loo_m = _to_host(res["loo_i"]).astype(np.float64)
