@@ -3,8 +3,40 @@
 Inputs may be NumPy arrays (host memory: the library stages them through the device) or
 torch CUDA tensors (device memory: zero copies, work is enqueued on torch's current stream
 and results come back as CUDA tensors).  torch is used only for device memory and streams.
+
+Every method has one body.  What differs between the two kinds of memory -- pointers, allocation,
+counters, index lists, the stream -- lives in a memory-space object (:class:`_HostSpace`,
+:class:`_DeviceSpace`); how a matrix argument may lie in memory is a :class:`_Layout`, declared
+once below and named by the method that uses it:
+
+======================================  ============  =========================  =========================================
+method                                  layout        host array taken in place  CUDA tensor taken in place
+======================================  ============  =========================  =========================================
+psis_loo, waic                          _LOO          draws- or obs-fastest (1)  draws- or obs-fastest (1)
+group_sum, psis_loo_groups              _LOO          draws- or obs-fastest      draws- or obs-fastest
+loo_diag, loo_influence(loglik)         _LOO_DIAG     draws- or obs-fastest (1)  draws- or obs-fastest (2)
+lfo_ratios, lfo, relative_eff           _LFO          draws- or obs-fastest      the same, rows that overlap copied
+importance_weights                      _WEIGHTS      draws-fastest              draws- or obs-fastest, unchecked (3)
+mixis_*, gather_draws, psis_loo_draws   _IN_PLACE     draws- or obs-fastest      any strides
+loo_influence(log_weights)              _LOG_WEIGHTS  draws-fastest              any positive strides
+e_loo, e_loo_quantiles                  promoted      contiguous copies          equal strides, else contiguous copies (4)
+loo_pit                                 promoted      draws- or obs-fastest      own positive strides
+loo_diag_weights                        promoted      draws-fastest              own positive strides
+======================================  ============  =========================  =========================================
+
+(1) with ``rows`` only draws-fastest.  (2) also with ``rows``.  (3) neither the dimensions, the device nor the dtype of
+the tensor is checked.  (4) the tensors are not checked for being CUDA tensors; the other promoted pairs are.
+Any other layout is copied.  ``stride_obs`` of a one-row CUDA tensor is passed as torch reports it (_LOO, _WEIGHTS,
+_IN_PLACE, promoted), as ``n_draws`` (_LFO) or as ``max(n_draws, 1)`` (_LOO_DIAG, _LOG_WEIGHTS); of a one-row host array
+always as ``n_draws``.
+
+Outputs: the pointwise vectors of psis_loo, waic, psis_loo_groups, psis_loo_draws and glm(mode="loo") are allocated for
+``pointwise``, on the device also for ``aggregate`` alone.  ``agg`` is zero-filled by waic, reduce_pointwise and mixis_loo
+in both spaces, by psis_loo, psis_loo_groups and psis_loo_draws on the host only, by glm and kfold nowhere.  The Mix-IS,
+lfo and relative_eff vectors are zero-filled, every other output is uninitialised memory for the library to write.
 """
 
+import collections
 import ctypes as C
 import threading
 
@@ -19,6 +51,292 @@ _lock = threading.Lock()
 
 def _is_torch_tensor(a):
     return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+
+
+def _host(a):
+    """An array or a tensor (of any device) as an ndarray."""
+    return a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a)
+
+
+def _ptr(x):
+    """The address of an array or tensor, None for None (a ``void *`` argument or struct entry)."""
+    if x is None:
+        return None
+    return x.data_ptr() if _is_torch_tensor(x) else x.ctypes.data
+
+
+def _code(x):
+    """The dtype code of an array or tensor (a tensor that is not float64 counts as float32)."""
+    if _is_torch_tensor(x):
+        import torch
+
+        return _capi.PLA_F64 if x.dtype == torch.float64 else _capi.PLA_F32
+    return dtype_code(x.dtype)
+
+
+def _of_length(v, n, what):
+    if n is not None and len(v) != n:
+        raise ValueError(what.format(n=n, got=len(v)))
+    return v
+
+
+# host_obs: a host array with the observations fastest is taken in place (never together with ``rows``); device: "library"
+# (draws or observations fastest in place, else a copy), "positive" (any positive strides) or "in place" (any strides);
+# sees_rows: ``rows`` rules out an observations-fastest CUDA tensor; one_row: stride_obs of a one-row CUDA tensor is
+# max(n_draws, one_row), None: as torch reports it; no_overlap: rows of a CUDA tensor that overlap are copied apart;
+# checked: a tensor must be 2-D, CUDA, f64 or f32.
+_Layout = collections.namedtuple("_Layout", "host_obs device sees_rows one_row no_overlap checked", defaults=(False, None, False, True))
+_LOO = _Layout(True, "library", sees_rows=True)
+_LOO_DIAG = _Layout(True, "library", one_row=1)
+_LFO = _Layout(True, "library", one_row=0, no_overlap=True)
+_WEIGHTS = _Layout(False, "library", checked=False)
+_IN_PLACE = _Layout(True, "in place")
+_LOG_WEIGHTS = _Layout(False, "positive", one_row=1)
+
+
+def _host_obs_fastest(a):
+    n, s = a.shape
+    return n > 1 and s > 1 and a.strides[0] == a.itemsize and a.strides[1] % a.itemsize == 0 and a.strides[1] >= n * a.itemsize
+
+
+def _as_2d_host(a, allow_obs_fastest=False):
+    a = np.asarray(a)
+    if a.dtype not in (np.float64, np.float32):
+        a = a.astype(np.float64)
+    if a.ndim != 2:
+        raise ValueError("expected a 2-D (n_obs, n_draws) array")
+    if allow_obs_fastest and _host_obs_fastest(a):
+        return a  # a (chain, draw, *obs) buffer viewed as (obs, sample): the library takes it as it is
+    if a.shape[1] > 1 and a.strides[1] != a.itemsize:
+        a = np.ascontiguousarray(a)
+    if a.shape[0] > 1 and (a.strides[0] % a.itemsize != 0 or a.strides[0] < 0):
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def _host_strides(a):
+    """(stride_obs, stride_draw) in elements of a host matrix prepared by :func:`_as_2d_host`."""
+    n, s = a.shape
+    if _host_obs_fastest(a):
+        return 1, a.strides[1] // a.itemsize
+    return (a.strides[0] // a.itemsize if n > 1 else s), 1
+
+
+def _host_rows(rows, n_obs):
+    """Index list as contiguous int64, range-checked like NumPy indexing would (no negative wrap-around:
+    loo_subsample.py:266-271 rejects indices outside [0, n))."""
+    idx = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= n_obs):
+        raise IndexError(f"row indices must lie in [0, {n_obs}), got range [{idx.min()}, {idx.max()}]")
+    return idx
+
+
+def _host_draws(draw_index, n_draws):
+    """Draw index as contiguous int64, range-checked like :func:`_host_rows` (no negative wrap-around)."""
+    idx = np.ascontiguousarray(np.asarray(draw_index).reshape(-1), dtype=np.int64)
+    if idx.size == 0:
+        raise ValueError("draw_index is empty")
+    if idx.min() < 0 or idx.max() >= n_draws:
+        raise IndexError(f"draw indices must lie in [0, {n_draws}), got range [{idx.min()}, {idx.max()}]")
+    return idx
+
+
+def _draws_fastest(t):
+    """ArviZ keeps log-likelihoods as (chain, draw, *obs): the (obs, sample) view of such a buffer has the
+    observations fastest.  The entry points of the library take that layout as it is (a tiled transpose kernel
+    feeds the row kernels block by block); this copy is only for layouts the library would walk with strides
+    (if the copy does not fit, the strided general kernel takes them)."""
+    import torch
+
+    if t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1:
+        try:
+            return t.contiguous()
+        except torch.OutOfMemoryError:  # pragma: no cover - needs a nearly full device
+            return t
+    return t
+
+
+def _library_layout(t, rows=None):
+    """Layouts the library reads fast without a copy: draws fastest, or observations fastest (stride 1 along
+    the observations, no row selection); anything else goes through :func:`_draws_fastest`."""
+    if t.dim() == 2 and t.shape[0] > 1 and t.shape[1] > 1 and t.stride(0) == 1 and t.stride(1) >= t.shape[0] and rows is None:
+        return t
+    return _draws_fastest(t)
+
+
+class _HostSpace:
+    """Host memory: NumPy arrays, which the library stages through the device.  Counters are one int64 passed by pointer
+    and read back as ``int``; index lists are range-checked."""
+
+    mem_space, stream, device = PLA_HOST, None, None
+    ptr, rows, draws, strides = staticmethod(_ptr), staticmethod(_host_rows), staticmethod(_host_draws), staticmethod(_host_strides)
+
+    @staticmethod
+    def new(shape, dtype="float64", zero=False):
+        return (np.zeros if zero else np.empty)(shape, dtype=dtype)
+
+    def counter(self):
+        return self.new(1, "int64", zero=True)
+
+    @staticmethod
+    def read(counter):
+        return int(counter[0])
+
+    @staticmethod
+    def f64(x):
+        return np.asarray(x, dtype=np.float64)
+
+    @staticmethod
+    def vector(v, n=None, what="", dtype="float64"):
+        """``v`` as a contiguous 1-D array (None stays None) of ``n`` values, else ``ValueError(what)``."""
+        return None if v is None else _of_length(np.ascontiguousarray(np.asarray(v, dtype=dtype).reshape(-1)), n, what)
+
+    @staticmethod
+    def index(index):
+        """(offsets, members) of a GroupIndex as contiguous int64 arrays."""
+        return tuple(np.ascontiguousarray(_host(a), dtype=np.int64) for a in (index.offsets, index.members))
+
+    @staticmethod
+    def matrix(a, layout, rows):
+        a = _as_2d_host(a, layout.host_obs and rows is None)
+        return (a, *_host_strides(a))
+
+    @staticmethod
+    def dense(a):
+        """A (rows, P) matrix and its strides: as it lies, as the ``.T`` view of a dense (P, rows) array, else a copy."""
+        if a.flags.c_contiguous:
+            return a, (a.shape[1], 1)
+        if a.T.flags.c_contiguous:
+            return a, (1, a.shape[0])
+        return np.ascontiguousarray(a), (a.shape[1], 1)
+
+    @staticmethod
+    def promoted(mats, names, own_strides, host_obs):
+        mats = [np.asarray(m) for m in mats]
+        if any(m.ndim != 2 or m.shape != mats[0].shape for m in mats):
+            raise ValueError(f"{names} must be 2-D arrays of one shape")
+        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
+        if not own_strides:
+            return [np.ascontiguousarray(m, dtype=dt) for m in mats]
+        return [_as_2d_host(m if m.dtype == dt else m.astype(dt), host_obs) for m in mats]
+
+
+class _DeviceSpace:
+    """The memory of one GPU: CUDA tensors, read in place; work goes onto torch's current stream and nothing is
+    synchronised.  Counters are one-element int64 tensors and come back as they are; index lists that are CUDA tensors
+    already are trusted (the kernels clamp)."""
+
+    mem_space = PLA_DEVICE
+    ptr = staticmethod(_ptr)
+
+    def __init__(self, engine, device):
+        self._engine, self.device = engine, device
+
+    @property
+    def stream(self):
+        return self._engine._stream().value
+
+    def new(self, shape, dtype="float64", zero=False):
+        import torch
+
+        return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, dtype) if isinstance(dtype, str) else dtype,
+                                                      device=self.device)
+
+    def counter(self):
+        return self.new(1, "int64", zero=True)
+
+    @staticmethod
+    def read(counter):
+        return counter
+
+    def f64(self, x):
+        import torch
+
+        return torch.as_tensor(x, device=self.device).to(torch.float64)
+
+    def vector(self, v, n=None, what="", dtype="float64"):
+        import torch
+
+        if v is None:
+            return None
+        return _of_length(torch.as_tensor(v, device=self.device).to(getattr(torch, dtype)).reshape(-1).contiguous(), n, what)
+
+    def rows(self, rows, n_obs):
+        import torch
+
+        if _is_torch_tensor(rows):  # already on the device: the kernels clamp, the caller vouches for the range
+            return rows.to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+        return torch.from_numpy(_host_rows(rows, n_obs)).to(self.device)
+
+    def draws(self, draw_index, n_draws):
+        import torch
+
+        if _is_torch_tensor(draw_index) and draw_index.is_cuda:  # used as it is: the kernel clamps, the caller vouches for the range
+            idx = draw_index.to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+            if idx.numel() == 0:
+                raise ValueError("draw_index is empty")
+            return idx
+        if _is_torch_tensor(draw_index):
+            draw_index = draw_index.numpy()
+        return torch.from_numpy(_host_draws(draw_index, n_draws)).to(self.device)
+
+    def index(self, index):
+        import torch
+
+        return tuple((a if _is_torch_tensor(a) else torch.from_numpy(np.asarray(a))).to(device=self.device, dtype=torch.int64).contiguous()
+                     for a in (index.offsets, index.members))
+
+    @staticmethod
+    def strides(t):
+        return t.stride()
+
+    @staticmethod
+    def matrix(t, layout, rows):
+        import torch
+
+        if layout.checked:
+            if t.dim() != 2 or not t.is_cuda:
+                raise ValueError("expected a 2-D CUDA tensor")
+            if t.dtype not in (torch.float64, torch.float32):
+                raise TypeError(f"unsupported dtype {t.dtype}")
+        if layout.device == "library":
+            t = _library_layout(t, rows if layout.sees_rows else None)
+            if layout.no_overlap and t.shape[1] > 1 and t.stride(1) == 1 and t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                t = t.contiguous()  # (rows that overlap: an expanded tensor)
+        elif layout.device == "positive" and min(t.stride()) <= 0:
+            t = t.contiguous()
+        n, s = t.shape
+        return t, (t.stride(0) if n > 1 or layout.one_row is None else max(s, layout.one_row)), t.stride(1)
+
+    @staticmethod
+    def dense(t):
+        t = t if min(t.stride()) > 0 else t.contiguous()
+        return t, t.stride()
+
+    @staticmethod
+    def promoted(mats, names, own_strides, host_obs):
+        import torch
+
+        if (any(not _is_torch_tensor(m) or m.dim() != 2 or m.shape != mats[0].shape for m in mats)
+                or (own_strides and not all(m.is_cuda for m in mats))):
+            raise ValueError(f"{names} must be 2-D CUDA tensors of one shape")
+        dt = torch.float64 if any(m.dtype == torch.float64 for m in mats) else torch.float32
+        mats = [m.to(dt) for m in mats]
+        if own_strides:
+            return [m if min(m.stride()) > 0 else m.contiguous() for m in mats]
+        if any(m.stride() != mats[0].stride() for m in mats) or mats[0].stride(1) <= 0:
+            mats = [m.contiguous() for m in mats]
+        return mats
+
+
+_HOST = _HostSpace()
+
+
+def _pointwise(sp, m, pointwise, aggregate, count=3):
+    """The pointwise outputs of a LOO-type pass; a device pass takes them for the aggregate alone too."""
+    if pointwise or (aggregate and sp.device is not None):
+        return [sp.new(m) for _ in range(count)]
+    return [None] * count
 
 
 class Engine:
@@ -55,56 +373,27 @@ class Engine:
 
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    @staticmethod
-    def _as_2d_host(a, allow_obs_fastest=False):
-        a = np.asarray(a)
-        if a.dtype not in (np.float64, np.float32):
-            a = a.astype(np.float64)
-        if a.ndim != 2:
-            raise ValueError("expected a 2-D (n_obs, n_draws) array")
-        if allow_obs_fastest and Engine._host_obs_fastest(a):
-            return a  # a (chain, draw, *obs) buffer viewed as (obs, sample): the library takes it as it is
-        if a.shape[1] > 1 and a.strides[1] != a.itemsize:
-            a = np.ascontiguousarray(a)
-        if a.shape[0] > 1 and (a.strides[0] % a.itemsize != 0 or a.strides[0] < 0):
-            a = np.ascontiguousarray(a)
-        return a
+    _host_draws = staticmethod(_host_draws)
 
-    @staticmethod
-    def _host_obs_fastest(a):
-        n, s = a.shape
-        return n > 1 and s > 1 and a.strides[0] == a.itemsize and a.strides[1] % a.itemsize == 0 and a.strides[1] >= n * a.itemsize
+    def _space(self, x):
+        """The memory space of an input: the device of a tensor, the host for anything else."""
+        return _DeviceSpace(self, x.device) if _is_torch_tensor(x) else _HOST
 
-    @staticmethod
-    def _host_strides(a):
-        """(stride_obs, stride_draw) in elements of a host matrix prepared by :meth:`_as_2d_host`."""
-        n, s = a.shape
-        if Engine._host_obs_fastest(a):
-            return 1, a.strides[1] // a.itemsize
-        return (a.strides[0] // a.itemsize if n > 1 else s), 1
+    def _matrix(self, x, layout, rows=None):
+        """An (n_obs, n_draws) matrix argument under ``layout`` -> ``(space, matrix, (dtype code, n_obs, n_draws, stride_obs,
+        stride_draw))``: the matrix as the library is to read it (to be kept alive over the call) and the five arguments that
+        follow its pointer in every entry point."""
+        sp = self._space(x)
+        a, so, sd = sp.matrix(x, layout, rows)
+        return sp, a, (_code(a), a.shape[0], a.shape[1], so, sd)
 
-    @staticmethod
-    def _draws_fastest(t):
-        """ArviZ keeps log-likelihoods as (chain, draw, *obs): the (obs, sample) view of such a buffer has the
-        observations fastest.  The entry points of the library take that layout as it is (a tiled transpose kernel
-        feeds the row kernels block by block); this copy is only for layouts the library would walk with strides
-        (if the copy does not fit, the strided general kernel takes them)."""
-        import torch
-
-        if t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1:
-            try:
-                return t.contiguous()
-            except torch.OutOfMemoryError:  # pragma: no cover - needs a nearly full device
-                return t
-        return t
-
-    @staticmethod
-    def _library_layout(t, rows=None):
-        """Layouts the library reads fast without a copy: draws fastest, or observations fastest (stride 1 along
-        the observations, no row selection); anything else goes through :meth:`_draws_fastest`."""
-        if t.dim() == 2 and t.shape[0] > 1 and t.shape[1] > 1 and t.stride(0) == 1 and t.stride(1) >= t.shape[0] and rows is None:
-            return t
-        return Engine._draws_fastest(t)
+    def _promoted(self, mats, names, own_strides, host_obs=False):
+        """Two or three matrices of one shape, promoted to one dtype (f64 if any is) -> ``(space, matrices, dtype code, n_obs,
+        n_draws)``.  ``own_strides``: each keeps its layout and is passed with ``space.strides`` of its own; otherwise all share
+        the strides of the first."""
+        sp = self._space(mats[0])
+        mats = sp.promoted(mats, names, own_strides, host_obs)
+        return sp, mats, _code(mats[0]), mats[0].shape[0], mats[0].shape[1]
 
     # ------------------------------------------------------------------ LOO pass
     def psis_loo(self, ll, tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True,
@@ -117,127 +406,33 @@ class Engine:
         (``pla_psis_loo_rows``) and the outputs have one entry per index.
         """
         mcode = METHOD_CODES[method]
-        if _is_torch_tensor(ll):
-            return self._psis_loo_device(ll, tail_count, mcode, scale_value, good_k, pointwise, aggregate, rows)
-        a = self._as_2d_host(ll, allow_obs_fastest=rows is None)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        if rows is not None:
-            idx = self._host_rows(rows, n)
-            m = idx.size
-            diag, loo_i, lppd_i = (np.empty(m), np.empty(m), np.empty(m)) if pointwise else (None, None, None)
-            agg = np.zeros(AGG_COUNT) if aggregate else None
-            p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-            check(self._lib.pla_psis_loo_rows(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, 1,
-                                              p(idx), m, mcode, int(tail_count), float(scale_value), float(good_k),
-                                              PLA_HOST, None, p(diag), p(loo_i), p(lppd_i), p(agg)))
-            return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg}
-        diag = np.empty(n) if pointwise else None
-        loo_i = np.empty(n) if pointwise else None
-        lppd_i = np.empty(n) if pointwise else None
-        agg = np.zeros(AGG_COUNT) if aggregate else None
-        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_psis_loo(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd,
-                                     mcode, int(tail_count), float(scale_value), float(good_k), PLA_HOST,
-                                     None, p(diag), p(loo_i), p(lppd_i), p(agg)))
-        return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg}
-
-    @staticmethod
-    def _host_rows(rows, n_obs):
-        """Index list as contiguous int64, range-checked like NumPy indexing would (no negative wrap-around:
-        loo_subsample.py:266-271 rejects indices outside [0, n))."""
-        idx = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
-        if idx.size and (idx.min() < 0 or idx.max() >= n_obs):
-            raise IndexError(f"row indices must lie in [0, {n_obs}), got range [{idx.min()}, {idx.max()}]")
-        return idx
-
-    def _device_rows(self, rows, n_obs, device):
-        import torch
-
-        if _is_torch_tensor(rows):  # already on the device: the kernels clamp, the caller vouches for the range
-            return rows.to(device=device, dtype=torch.int64).contiguous().reshape(-1)
-        return torch.from_numpy(self._host_rows(rows, n_obs)).to(device)
-
-    def _psis_loo_device(self, t, tail_count, mcode, scale_value, good_k, pointwise, aggregate, rows=None):
-        import torch
-
-        if t.dim() != 2 or not t.is_cuda:
-            raise ValueError("expected a 2-D CUDA tensor")
-        if t.dtype not in (torch.float64, torch.float32):
-            raise TypeError(f"unsupported dtype {t.dtype}")
-        t = self._library_layout(t, rows)
-        n, s = t.shape
-        dev = t.device
-        idx = None if rows is None else self._device_rows(rows, n, dev)
-        m = n if idx is None else idx.numel()
-        diag = torch.empty(m, dtype=torch.float64, device=dev) if (pointwise or aggregate) else None
-        loo_i = torch.empty(m, dtype=torch.float64, device=dev) if (pointwise or aggregate) else None
-        lppd_i = torch.empty(m, dtype=torch.float64, device=dev) if (pointwise or aggregate) else None
-        agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev) if aggregate else None  # (every slot is written)
-        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-        code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-        if idx is not None:
-            check(self._lib.pla_psis_loo_rows(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
-                                              p(idx), m, mcode, int(tail_count), float(scale_value), float(good_k),
-                                              PLA_DEVICE, self._stream(), p(diag), p(loo_i), p(lppd_i), p(agg)))
-            return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg}
-        check(self._lib.pla_psis_loo(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
-                                     mcode, int(tail_count), float(scale_value), float(good_k), PLA_DEVICE,
-                                     self._stream(), p(diag), p(loo_i), p(lppd_i), p(agg)))
+        sp, a, dims = self._matrix(ll, _LOO, rows)
+        idx = None if rows is None else sp.rows(rows, dims[1])
+        m = dims[1] if idx is None else len(idx)
+        diag, loo_i, lppd_i = _pointwise(sp, m, pointwise, aggregate)
+        agg = sp.new(AGG_COUNT, zero=sp.device is None) if aggregate else None  # (the device pass writes every slot)
+        p = sp.ptr
+        tail = (mcode, int(tail_count), float(scale_value), float(good_k), sp.mem_space, sp.stream, p(diag), p(loo_i), p(lppd_i), p(agg))
+        if idx is None:
+            check(self._lib.pla_psis_loo(self._h, p(a), *dims, *tail))
+        else:
+            check(self._lib.pla_psis_loo_rows(self._h, p(a), *dims, p(idx), m, *tail))
         return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg}
 
     # ------------------------------------------------------------------ leave-one-group-out
-    @staticmethod
-    def _host_index(index):
-        """(offsets, members) of a GroupIndex as contiguous host int64 arrays."""
-        conv = lambda a: np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a), dtype=np.int64)  # noqa: E731
-        return conv(index.offsets), conv(index.members)
-
-    @staticmethod
-    def _device_index(index, device):
-        import torch
-
-        conv = lambda a: (a if _is_torch_tensor(a) else torch.from_numpy(np.asarray(a))).to(device=device, dtype=torch.int64).contiguous()  # noqa: E731
-        return conv(index.offsets), conv(index.members)
-
-    def _groups_input(self, ll):
-        import torch
-
-        if ll.dim() != 2 or not ll.is_cuda:
-            raise ValueError("expected a 2-D CUDA tensor")
-        if ll.dtype not in (torch.float64, torch.float32):
-            raise TypeError(f"unsupported dtype {ll.dtype}")
-        return self._library_layout(ll)
-
     def group_sum(self, ll, index):
         """(n_obs, n_draws) matrix + :class:`~pyloo_amd.loo_group.GroupIndex` -> ``(sums, n_replaced)`` (``pla_group_sum``):
         ``sums[g]`` = the rows of group g's members added in ascending order, in the matrix's dtype (bitwise NumPy's
         ``ll[members].sum(axis=0)``), NaN counted as -1e10.  NumPy in -> ``(ndarray, int)``; CUDA tensor in -> ``(tensor, int64
         tensor of one element)``, nothing synchronised."""
         G = int(index.n_groups)
-        if _is_torch_tensor(ll):
-            import torch
-
-            t = self._groups_input(ll)
-            n, s = t.shape
-            off, mem = self._device_index(index, t.device)
-            out = torch.empty((G, s), dtype=t.dtype, device=t.device)
-            nrep = torch.zeros(1, dtype=torch.int64, device=t.device)
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_group_sum(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
-                                          C.c_void_p(off.data_ptr()), C.c_void_p(mem.data_ptr()), G, PLA_DEVICE, self._stream(),
-                                          C.c_void_p(out.data_ptr()), C.c_void_p(nrep.data_ptr())))
-            return out, nrep
-        a = self._as_2d_host(ll, allow_obs_fastest=True)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        off, mem = self._host_index(index)
-        out = np.empty((G, s), dtype=a.dtype)
-        nrep = C.c_int64(0)
-        check(self._lib.pla_group_sum(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd,
-                                      off.ctypes.data_as(C.c_void_p), mem.ctypes.data_as(C.c_void_p), G, PLA_HOST, None,
-                                      out.ctypes.data_as(C.c_void_p), C.byref(nrep)))
-        return out, int(nrep.value)
+        sp, a, dims = self._matrix(ll, _LOO)
+        off, mem = sp.index(index)
+        out = sp.new((G, dims[2]), a.dtype)
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_group_sum(self._h, p(a), *dims, p(off), p(mem), G, sp.mem_space, sp.stream, p(out), p(nrep)))
+        return out, sp.read(nrep)
 
     def psis_loo_groups(self, ll, index, tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True):
         """Leave-one-group-out pass (``pla_psis_loo_groups``): group sums, then the PSIS / SIS / TIS pass over them.
@@ -246,100 +441,33 @@ class Engine:
         for NumPy input, CUDA tensors for CUDA-tensor input (nothing synchronised)."""
         mcode = METHOD_CODES[method]
         G = int(index.n_groups)
-        if _is_torch_tensor(ll):
-            import torch
-
-            t = self._groups_input(ll)
-            n, s = t.shape
-            dev = t.device
-            off, mem = self._device_index(index, dev)
-            mk = lambda: torch.empty(G, dtype=torch.float64, device=dev)  # noqa: E731
-            diag, logo_i, lppd_i = (mk(), mk(), mk()) if (pointwise or aggregate) else (None, None, None)
-            agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev) if aggregate else None
-            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
-            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_psis_loo_groups(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1), p(off), p(mem),
-                                                G, mcode, int(tail_count), float(scale_value), float(good_k), PLA_DEVICE,
-                                                self._stream(), p(diag), p(logo_i), p(lppd_i), p(agg), p(nrep)))
-            return {"diag": diag, "logo_i": logo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": nrep}
-        a = self._as_2d_host(ll, allow_obs_fastest=True)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        off, mem = self._host_index(index)
-        diag, logo_i, lppd_i = (np.empty(G), np.empty(G), np.empty(G)) if pointwise else (None, None, None)
-        agg = np.zeros(AGG_COUNT) if aggregate else None
-        nrep = C.c_int64(0)
-        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_psis_loo_groups(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd, p(off), p(mem), G,
-                                            mcode, int(tail_count), float(scale_value), float(good_k), PLA_HOST, None, p(diag),
-                                            p(logo_i), p(lppd_i), p(agg), C.byref(nrep)))
-        return {"diag": diag, "logo_i": logo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": int(nrep.value)}
+        sp, a, dims = self._matrix(ll, _LOO)
+        off, mem = sp.index(index)
+        diag, logo_i, lppd_i = _pointwise(sp, G, pointwise, aggregate)
+        agg = sp.new(AGG_COUNT, zero=sp.device is None) if aggregate else None
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_psis_loo_groups(self._h, p(a), *dims, p(off), p(mem), G, mcode, int(tail_count), float(scale_value),
+                                            float(good_k), sp.mem_space, sp.stream, p(diag), p(logo_i), p(lppd_i), p(agg), p(nrep)))
+        return {"diag": diag, "logo_i": logo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": sp.read(nrep)}
 
     # ------------------------------------------------------------------ approximate posteriors: draws through an index
-    @staticmethod
-    def _host_draws(draw_index, n_draws):
-        """Draw index as contiguous int64, range-checked like :meth:`_host_rows` (no negative wrap-around)."""
-        idx = np.ascontiguousarray(np.asarray(draw_index).reshape(-1), dtype=np.int64)
-        if idx.size == 0:
-            raise ValueError("draw_index is empty")
-        if idx.min() < 0 or idx.max() >= n_draws:
-            raise IndexError(f"draw indices must lie in [0, {n_draws}), got range [{idx.min()}, {idx.max()}]")
-        return idx
-
-    def _device_draws(self, draw_index, n_draws, device):
-        import torch
-
-        if _is_torch_tensor(draw_index) and draw_index.is_cuda:  # used as it is: the kernel clamps, the caller vouches for the range
-            idx = draw_index.to(device=device, dtype=torch.int64).contiguous().reshape(-1)
-            if idx.numel() == 0:
-                raise ValueError("draw_index is empty")
-            return idx
-        if _is_torch_tensor(draw_index):
-            draw_index = draw_index.numpy()
-        return torch.from_numpy(self._host_draws(draw_index, n_draws)).to(device)
-
-    @staticmethod
-    def _draws_input(ll):
-        import torch
-
-        if ll.dim() != 2 or not ll.is_cuda:
-            raise ValueError("expected a 2-D CUDA tensor")
-        if ll.dtype not in (torch.float64, torch.float32):
-            raise TypeError(f"unsupported dtype {ll.dtype}")
-        return ll  # (every strided view is read in place: pla_gather_draws takes any positive strides)
-
     def gather_draws(self, ll, draw_index, out=None):
         """(n_obs, n_draws) matrix + draw index -> ``(matrix, n_replaced)`` (``pla_gather_draws``): bitwise ``ll[:, draw_index]`` in
         the matrix's dtype, draws contiguous, NaN written as -1e10 and counted.  NumPy in -> ``(ndarray, int)``; CUDA tensor in ->
         ``(tensor, int64 tensor of one element)``, nothing synchronised.  ``out``: a contiguous CUDA tensor to write into."""
-        if _is_torch_tensor(ll):
-            import torch
-
-            t = self._draws_input(ll)
-            n, s = t.shape
-            idx = self._device_draws(draw_index, s, t.device)
-            m = idx.numel()
-            if out is None:
-                out = torch.empty((n, m), dtype=t.dtype, device=t.device)
-            elif tuple(out.shape) != (n, m) or out.dtype != t.dtype or not out.is_contiguous() or out.device != t.device:
-                raise ValueError("out must be a contiguous tensor of shape (n_obs, len(draw_index)) with the matrix's dtype and device")
-            nrep = torch.zeros(1, dtype=torch.int64, device=t.device)
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_gather_draws(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
-                                             C.c_void_p(idx.data_ptr()), m, PLA_DEVICE, self._stream(), C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(nrep.data_ptr())))
-            return out, nrep
-        a = self._as_2d_host(ll, allow_obs_fastest=True)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        idx = self._host_draws(draw_index, s)
-        res = np.empty((n, idx.size), dtype=a.dtype)
-        nrep = C.c_int64(0)
-        check(self._lib.pla_gather_draws(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd,
-                                         idx.ctypes.data_as(C.c_void_p), idx.size, PLA_HOST, None, res.ctypes.data_as(C.c_void_p),
-                                         C.byref(nrep)))
-        return res, int(nrep.value)
+        sp, a, dims = self._matrix(ll, _IN_PLACE)
+        n, s = dims[1:3]
+        idx = sp.draws(draw_index, s)
+        m = len(idx)
+        if out is None or sp.device is None:
+            out = sp.new((n, m), a.dtype)
+        elif tuple(out.shape) != (n, m) or out.dtype != a.dtype or not out.is_contiguous() or out.device != a.device:
+            raise ValueError("out must be a contiguous tensor of shape (n_obs, len(draw_index)) with the matrix's dtype and device")
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_gather_draws(self._h, p(a), *dims, p(idx), m, sp.mem_space, sp.stream, p(out), p(nrep)))
+        return out, sp.read(nrep)
 
     def psis_loo_draws(self, ll, draw_index, tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True):
         """PSIS / SIS / TIS pass over ``ll[:, draw_index]`` (``pla_psis_loo_draws``) without materialising that matrix: blocks of
@@ -348,35 +476,15 @@ class Engine:
         Returns ``dict(diag, loo_i, lppd_i, agg, n_replaced)`` -- NumPy arrays (and an int) for NumPy input, CUDA tensors for
         CUDA-tensor input (nothing synchronised)."""
         mcode = METHOD_CODES[method]
-        if _is_torch_tensor(ll):
-            import torch
-
-            t = self._draws_input(ll)
-            n, s = t.shape
-            dev = t.device
-            idx = self._device_draws(draw_index, s, dev)
-            mk = lambda: torch.empty(n, dtype=torch.float64, device=dev)  # noqa: E731
-            diag, loo_i, lppd_i = (mk(), mk(), mk()) if (pointwise or aggregate) else (None, None, None)
-            agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev) if aggregate else None
-            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
-            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_psis_loo_draws(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1), p(idx),
-                                               idx.numel(), mcode, int(tail_count), float(scale_value), float(good_k), PLA_DEVICE,
-                                               self._stream(), p(diag), p(loo_i), p(lppd_i), p(agg), p(nrep)))
-            return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": nrep}
-        a = self._as_2d_host(ll, allow_obs_fastest=True)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        idx = self._host_draws(draw_index, s)
-        diag, loo_i, lppd_i = (np.empty(n), np.empty(n), np.empty(n)) if pointwise else (None, None, None)
-        agg = np.zeros(AGG_COUNT) if aggregate else None
-        nrep = C.c_int64(0)
-        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_psis_loo_draws(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd, p(idx), idx.size,
-                                           mcode, int(tail_count), float(scale_value), float(good_k), PLA_HOST, None, p(diag),
-                                           p(loo_i), p(lppd_i), p(agg), C.byref(nrep)))
-        return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": int(nrep.value)}
+        sp, a, dims = self._matrix(ll, _IN_PLACE)
+        idx = sp.draws(draw_index, dims[2])
+        diag, loo_i, lppd_i = _pointwise(sp, dims[1], pointwise, aggregate)
+        agg = sp.new(AGG_COUNT, zero=sp.device is None) if aggregate else None
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_psis_loo_draws(self._h, p(a), *dims, p(idx), len(idx), mcode, int(tail_count), float(scale_value),
+                                           float(good_k), sp.mem_space, sp.stream, p(diag), p(loo_i), p(lppd_i), p(agg), p(nrep)))
+        return {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": agg, "n_replaced": sp.read(nrep)}
 
     # ------------------------------------------------------------------ k-fold cross-validation
     @staticmethod
@@ -386,11 +494,12 @@ class Engine:
             raise ValueError("expected 2-D (n_obs, n_draws) matrices")
         return a if a.dtype in (np.float64, np.float32) else a.astype(np.float64)
 
-    def _kfold_upload(self, a, device, rows=None):
+    @staticmethod
+    def _kfold_upload(a, device, rows=None):
         """A host matrix on the device in the layout it has in memory (observations fastest stays so), cut to ``rows`` first."""
         import torch
 
-        if self._host_obs_fastest(a):
+        if _host_obs_fastest(a):
             base = a.T if rows is None else a.T[:, rows]
             return torch.from_numpy(np.ascontiguousarray(base)).to(device).T
         return torch.from_numpy(np.ascontiguousarray(a if rows is None else a[rows])).to(device)
@@ -438,7 +547,7 @@ class Engine:
         folds_dev = _is_torch_tensor(folds) and folds.is_cuda
         fh = None
         if not folds_dev or any(f and not d for f, d in zip(full_form, on_device[1:])):
-            fh = (folds.detach().cpu().numpy() if _is_torch_tensor(folds) else np.asarray(folds)).reshape(-1).astype(np.int64)
+            fh = _host(folds).reshape(-1).astype(np.int64)
             if fh.size != N:
                 raise ValueError(f"Length of folds ({fh.size}) must match observations ({N})")
             if fh.min() < 1 or fh.max() > K:
@@ -484,31 +593,23 @@ class Engine:
 
     def _kfold_lme(self, plan, nan_flag=True):
         """The ragged pass (``pla_kfold_lme``): ``(out, n_replaced)``, ``out[:N]`` the full fit's values, ``out[N:]`` the held-out ones."""
-        import torch
-
-        N, dev = plan["N"], plan["dev"]
-        out = torch.empty(2 * N, dtype=torch.float64, device=dev)
-        nrep = torch.zeros(1, dtype=torch.int64, device=dev)
-        pn = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        pt = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        check(self._lib.pla_kfold_lme(self._h, *(pn(a) for a in plan["table"]), plan["K"] + 1,
-                                      _capi.PLA_F32 if plan["f32"] else _capi.PLA_F64, 1 if nan_flag else 0, pt(plan["offsets"]),
-                                      pt(plan["task_row"]), pt(plan["task_out"]), 2 * N, PLA_DEVICE, self._stream(), pt(out), 2 * N,
-                                      pt(nrep)))
+        N, sp = plan["N"], _DeviceSpace(self, plan["dev"])
+        out = sp.new(2 * N)
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_kfold_lme(self._h, *(p(a) for a in plan["table"]), plan["K"] + 1, _code(plan["mats"][0]),
+                                      1 if nan_flag else 0, p(plan["offsets"]), p(plan["task_row"]), p(plan["task_out"]), 2 * N,
+                                      sp.mem_space, sp.stream, p(out), 2 * N, p(nrep)))
         return out, nrep
 
     def _kfold_finish(self, plan, out, nrep, scale_value):
         """The finishing pass (``pla_kfold_reduce``) and the result dictionary of :meth:`kfold`."""
-        import torch
-
-        N, dev = plan["N"], plan["dev"]
-        pt = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        N, sp = plan["N"], _DeviceSpace(self, plan["dev"])
         lpd_full_i, elpd_i = out[:N], out[N:]
-        p_i = torch.empty(N, dtype=torch.float64, device=dev)
-        kfold_i = torch.empty(N, dtype=torch.float64, device=dev)
-        agg = torch.empty(AGG_COUNT, dtype=torch.float64, device=dev)
-        check(self._lib.pla_kfold_reduce(self._h, pt(elpd_i), pt(lpd_full_i), N, float(scale_value), pt(nrep), PLA_DEVICE,
-                                         self._stream(), pt(p_i), pt(kfold_i), pt(agg)))
+        p_i, kfold_i, agg = sp.new(N), sp.new(N), sp.new(AGG_COUNT)
+        p = sp.ptr
+        check(self._lib.pla_kfold_reduce(self._h, p(elpd_i), p(lpd_full_i), N, float(scale_value), p(nrep), sp.mem_space, sp.stream,
+                                         p(p_i), p(kfold_i), p(agg)))
         res = {"elpd_i": elpd_i, "lpd_full_i": lpd_full_i, "p_i": p_i, "kfold_i": kfold_i, "agg": agg}
         if not plan["host_out"]:
             return res
@@ -540,26 +641,23 @@ class Engine:
         plain mean, weighted mean ``sum exp(lw) x``, ``np.var`` and the raw weighted second moment of ``shift_and_scale``;
         ``covs`` (B, 2, D, D) = ``np.cov(rowvar=False)`` and ``np.cov(aweights=exp(lw))``, or None without ``cov``.  Nothing is
         synchronised; the bits depend neither on B nor on the grid."""
-        import torch
-
         if not _is_torch_tensor(upars) or upars.dim() != 3:
             raise ValueError("upars: expected a (B, S, D) CUDA tensor")
         B, S, D = (int(v) for v in upars.shape)
         self.mm_check_dim(D, cov)
         x = self._mm_input(upars, (B, S, D), "upars")
         w = self._mm_input(lw, (B, S), "lw")
-        stats = torch.empty((B, 4, D), dtype=torch.float64, device=x.device)
-        covs = torch.empty((B, 2, D, D), dtype=torch.float64, device=x.device) if cov else None
-        check(self._lib.pla_mm_moments(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), B, S, D, 1 if cov else 0,
-                                       self._stream(), C.c_void_p(stats.data_ptr()), C.c_void_p(covs.data_ptr()) if cov else None))
+        sp = self._space(x)
+        stats = sp.new((B, 4, D))
+        covs = sp.new((B, 2, D, D)) if cov else None
+        p = sp.ptr
+        check(self._lib.pla_mm_moments(self._h, p(x), p(w), B, S, D, 1 if cov else 0, sp.stream, p(stats), p(covs)))
         return stats, covs
 
     def mm_transform(self, x, m0, m1, pre=None, mapping=None, post_div=None, rows=None):
         """``out[b, s] = (((x[b, s] - m0[b]) * pre[b]) @ mapping[b].T) / post_div[b] + m1[b]`` for the rows ``s`` in ``rows = (lo, hi)``
         (default: all), ``x[b, s]`` for the others (``pla_mm_transform``).  ``x`` is (B, S, D), or (S, D) shared by every b;
         ``m0`` / ``m1`` / ``pre`` / ``post_div`` (B, D), ``mapping`` (B, D, D); CUDA f64.  Returns a new (B, S, D) tensor."""
-        import torch
-
         if not _is_torch_tensor(m0) or m0.dim() != 2:
             raise ValueError("m0: expected a (B, D) CUDA tensor")
         B, D = (int(v) for v in m0.shape)
@@ -571,10 +669,11 @@ class Engine:
         m0, m1, pre, post_div = vec(m0, "m0"), vec(m1, "m1"), vec(pre, "pre"), vec(post_div, "post_div")
         mapping = None if mapping is None else self._mm_input(mapping, (B, D, D), "mapping")
         lo, hi = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
-        out = torch.empty((B, S, D), dtype=torch.float64, device=x.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        sp = self._space(x)
+        out = sp.new((B, S, D))
+        p = sp.ptr
         check(self._lib.pla_mm_transform(self._h, p(x), 0 if shared else S * D, p(m0), p(pre), p(mapping), p(post_div), p(m1), B, S, D,
-                                         lo, hi, self._stream(), p(out)))
+                                         lo, hi, sp.stream, p(out)))
         return out
 
     def mm_ratios(self, mode, a, b, c=None, jac=None):
@@ -583,8 +682,6 @@ class Engine:
         ``lp - lp_orig``, NaN -> -inf; ``"split"``: a = ll_half, b = lp_half, c = lp_half_inv (B, S), jac (B, 2) -> (B, S);
         ``"sum"``: ``a + b`` with NaN / +inf -> -inf; ``"finish"``: a = ll, b = lw -> (B, 2) = ``logsumexp(ll + lw)``,
         ``logsumexp(ll) - log S``."""
-        import torch
-
         code = {"update": 0, "split": 1, "sum": 2, "finish": 3}[mode]
         if not _is_torch_tensor(a) or a.dim() != 2:
             raise ValueError("a: expected a (B, S) CUDA tensor")
@@ -596,36 +693,22 @@ class Engine:
             c, jac = self._mm_input(c, (B, S), "c"), self._mm_input(jac, (B, 2), "jac")
         else:
             c = jac = None
-        shape = {0: (2 * B, S), 1: (B, S), 2: (B, S), 3: (B, 2)}[code]
-        out = torch.empty(shape, dtype=torch.float64, device=a.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        check(self._lib.pla_mm_ratios(self._h, code, p(a), p(b), p(c), p(jac), B, S, self._stream(), p(out)))
+        sp = self._space(a)
+        out = sp.new({0: (2 * B, S), 1: (B, S), 2: (B, S), 3: (B, 2)}[code])
+        p = sp.ptr
+        check(self._lib.pla_mm_ratios(self._h, code, p(a), p(b), p(c), p(jac), B, S, sp.stream, p(out)))
         return out
 
     # ------------------------------------------------------------------ weights pass
     def importance_weights(self, logw, tail_count=0, method="psis"):
         """(n_obs, n_draws) log ratios -> (lw, diag) (``pla_importance_weights``)."""
         mcode = METHOD_CODES[method]
-        if _is_torch_tensor(logw):
-            import torch
-
-            t = self._library_layout(logw)
-            n, s = t.shape
-            lw = torch.empty((n, s), dtype=t.dtype, device=t.device)
-            diag = torch.empty(n, dtype=torch.float64, device=t.device)
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_importance_weights(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0),
-                                                   t.stride(1), mcode, int(tail_count), PLA_DEVICE, self._stream(),
-                                                   C.c_void_p(lw.data_ptr()), C.c_void_p(diag.data_ptr())))
-            return lw, diag
-        a = self._as_2d_host(logw)
-        n, s = a.shape
-        so = a.strides[0] // a.itemsize if n > 1 else s
-        lw = np.empty((n, s), dtype=a.dtype)
-        diag = np.empty(n)
-        check(self._lib.pla_importance_weights(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, 1,
-                                               mcode, int(tail_count), PLA_HOST, None,
-                                               lw.ctypes.data_as(C.c_void_p), diag.ctypes.data_as(C.c_void_p)))
+        sp, a, dims = self._matrix(logw, _WEIGHTS)
+        n, s = dims[1:3]
+        lw = sp.new((n, s), a.dtype)
+        diag = sp.new(n)
+        p = sp.ptr
+        check(self._lib.pla_importance_weights(self._h, p(a), *dims, mcode, int(tail_count), sp.mem_space, sp.stream, p(lw), p(diag)))
         return lw, diag
 
     # ------------------------------------------------------------------ WAIC pass
@@ -633,107 +716,50 @@ class Engine:
         """(n_obs, n_draws) log-likelihood -> ``dict(lppd_i, var_i, waic_i, agg)`` (``pla_waic``; the
         slots of ``agg`` are documented in include/pyloo_amd.h).  ``rows``: optional observation indices
         (``pla_waic_rows``), one output entry per index."""
-        if _is_torch_tensor(ll):
-            import torch
-
-            t = ll
-            if t.dim() != 2 or not t.is_cuda:
-                raise ValueError("expected a 2-D CUDA tensor")
-            if t.dtype not in (torch.float64, torch.float32):
-                raise TypeError(f"unsupported dtype {t.dtype}")
-            t = self._library_layout(t, rows)
-            n, s = t.shape
-            idx = None if rows is None else self._device_rows(rows, n, t.device)
-            m = n if idx is None else idx.numel()
-            mk = lambda: torch.empty(m, dtype=torch.float64, device=t.device)  # noqa: E731
-            lppd_i, var_i, waic_i = (mk(), mk(), mk()) if (pointwise or aggregate) else (None, None, None)
-            agg = torch.zeros(AGG_COUNT, dtype=torch.float64, device=t.device) if aggregate else None
-            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            if idx is not None:
-                check(self._lib.pla_waic_rows(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
-                                              p(idx), m, float(scale_value), PLA_DEVICE, self._stream(), p(lppd_i),
-                                              p(var_i), p(waic_i), p(agg)))
-                return {"lppd_i": lppd_i, "var_i": var_i, "waic_i": waic_i, "agg": agg}
-            check(self._lib.pla_waic(self._h, C.c_void_p(t.data_ptr()), code, n, s, t.stride(0), t.stride(1),
-                                     float(scale_value), PLA_DEVICE, self._stream(), p(lppd_i), p(var_i), p(waic_i), p(agg)))
-            return {"lppd_i": lppd_i, "var_i": var_i, "waic_i": waic_i, "agg": agg}
-        a = self._as_2d_host(ll, allow_obs_fastest=rows is None)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        idx = None if rows is None else self._host_rows(rows, n)
-        m = n if idx is None else idx.size
-        lppd_i, var_i, waic_i = (np.empty(m), np.empty(m), np.empty(m)) if pointwise else (None, None, None)
-        agg = np.zeros(AGG_COUNT) if aggregate else None
-        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        if idx is not None:
-            check(self._lib.pla_waic_rows(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, 1, p(idx), m,
-                                          float(scale_value), PLA_HOST, None, p(lppd_i), p(var_i), p(waic_i), p(agg)))
-            return {"lppd_i": lppd_i, "var_i": var_i, "waic_i": waic_i, "agg": agg}
-        check(self._lib.pla_waic(self._h, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), n, s, so, sd,
-                                 float(scale_value), PLA_HOST, None, p(lppd_i), p(var_i), p(waic_i), p(agg)))
+        sp, a, dims = self._matrix(ll, _LOO, rows)
+        idx = None if rows is None else sp.rows(rows, dims[1])
+        m = dims[1] if idx is None else len(idx)
+        lppd_i, var_i, waic_i = _pointwise(sp, m, pointwise, aggregate)
+        agg = sp.new(AGG_COUNT, zero=True) if aggregate else None
+        p = sp.ptr
+        tail = (float(scale_value), sp.mem_space, sp.stream, p(lppd_i), p(var_i), p(waic_i), p(agg))
+        if idx is None:
+            check(self._lib.pla_waic(self._h, p(a), *dims, *tail))
+        else:
+            check(self._lib.pla_waic_rows(self._h, p(a), *dims, p(idx), m, *tail))
         return {"lppd_i": lppd_i, "var_i": var_i, "waic_i": waic_i, "agg": agg}
 
     # ------------------------------------------------------------------ Mix-IS-LOO passes
-    def _mixis_input(self, ll):
-        """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None): a CUDA tensor is read in place
-        whatever its strides, a host array in either of the two layouts the library uploads."""
-        if _is_torch_tensor(ll):
-            import torch
-
-            if ll.dim() != 2 or not ll.is_cuda:
-                raise ValueError("expected a 2-D CUDA tensor")
-            if ll.dtype not in (torch.float64, torch.float32):
-                raise TypeError(f"unsupported dtype {ll.dtype}")
-            code = _capi.PLA_F64 if ll.dtype == torch.float64 else _capi.PLA_F32
-            return ll, ll.shape[0], ll.shape[1], ll.stride(0), ll.stride(1), code, PLA_DEVICE, self._stream(), ll.device
-        a = self._as_2d_host(ll, allow_obs_fastest=True)
-        so, sd = self._host_strides(a)
-        return a, a.shape[0], a.shape[1], so, sd, dtype_code(a.dtype), PLA_HOST, None, None
-
-    @staticmethod
-    def _mixis_ptr(x):
-        if x is None:
-            return None
-        return C.c_void_p(x.data_ptr()) if _is_torch_tensor(x) else x.ctypes.data_as(C.c_void_p)
-
-    @staticmethod
-    def _mixis_new(n, device, dtype="float64"):
-        if device is None:
-            return np.zeros(n, dtype=dtype)
-        import torch
-
-        return torch.zeros(n, dtype=getattr(torch, dtype), device=device)
-
     def mixis_draw_lse(self, ll):
         """Pass 1 of Mix-IS-LOO (``pla_mixis_draw_lse``): (n_obs, n_draws) log-likelihood -> ``dict(c, n_replaced)`` with
         ``c[s] = log sum_i exp(-ll[i, s])`` and the counts of NaN and of infinite entries met, where the matrix lives."""
-        a, n, s, so, sd, code, space, stream, device = self._mixis_input(ll)
-        c = self._mixis_new(s, device)
-        nrep = self._mixis_new(2, device, "int64")
-        p = self._mixis_ptr
-        check(self._lib.pla_mixis_draw_lse(self._h, p(a), code, n, s, so, sd, space, stream, p(c), p(nrep)))
+        sp, a, dims = self._matrix(ll, _IN_PLACE)
+        c = sp.new(dims[2], zero=True)
+        nrep = sp.new(2, "int64", zero=True)
+        p = sp.ptr
+        check(self._lib.pla_mixis_draw_lse(self._h, p(a), *dims, sp.mem_space, sp.stream, p(c), p(nrep)))
         return {"c": c, "n_replaced": nrep}
 
     def mixis_loo(self, ll, c=None, scale_value=1.0, pointwise=True, aggregate=True):
         """Mix-IS-LOO (``pla_mixis_loo``): ``dict(loo_i, c, agg)`` with ``loo_i = scale * (LSE_s(-c) - LSE_s(-ll[i, s] - c[s]))``.
         ``c``: the result of :meth:`mixis_draw_lse` (computed when None); the slots of ``agg`` are documented in
         include/pyloo_amd.h."""
-        a, n, s, so, sd, code, space, stream, device = self._mixis_input(ll)
+        sp, a, dims = self._matrix(ll, _IN_PLACE)
+        n, s = dims[1:3]
         if c is None:
             c = self.mixis_draw_lse(ll)["c"]
-        elif device is None:
+        elif sp.device is None:
             c = np.ascontiguousarray(c, dtype=np.float64)
         else:
             import torch
 
-            c = torch.as_tensor(c, dtype=torch.float64, device=device).contiguous()
+            c = torch.as_tensor(c, dtype=torch.float64, device=sp.device).contiguous()
         if c.shape != (s,):
             raise ValueError(f"c must have one entry per draw: expected ({s},), got {tuple(c.shape)}")
-        loo_i = self._mixis_new(n, device) if pointwise else None
-        agg = self._mixis_new(AGG_COUNT, device) if aggregate else None
-        p = self._mixis_ptr
-        check(self._lib.pla_mixis_loo(self._h, p(a), code, n, s, so, sd, p(c), float(scale_value), space, stream, p(loo_i), p(agg)))
+        loo_i = sp.new(n, zero=True) if pointwise else None
+        agg = sp.new(AGG_COUNT, zero=True) if aggregate else None
+        p = sp.ptr
+        check(self._lib.pla_mixis_loo(self._h, p(a), *dims, p(c), float(scale_value), sp.mem_space, sp.stream, p(loo_i), p(agg)))
         return {"loo_i": loo_i, "c": c, "agg": agg}
 
     def set_mixis_grid(self, max_workgroups):
@@ -752,36 +778,24 @@ class Engine:
     def e_loo(self, x, log_weights, log_ratios=None, tail_len=20):
         """(n_obs, n_draws) draws ``x`` + log-weights (+ raw log ratios) -> ``dict(mean, var, k_mean, k_var, k_none)``
         (``pla_e_loo``: e_loo.py:214-236 per observation).  NumPy in -> NumPy out; CUDA tensors in -> CUDA tensors out."""
-        if _is_torch_tensor(x):
-            import torch
+        mats = [x, log_weights] + ([log_ratios] if log_ratios is not None else [])
+        sp, mats, code, n, s = self._promoted(mats, "x, log_weights and log_ratios", own_strides=False)
+        keys = ("mean", "var", "k_mean", "k_var", "k_none")
+        out = {k: sp.new(n) for k in keys}
+        p = sp.ptr
+        check(self._lib.pla_e_loo(self._h, p(mats[0]), p(mats[1]), p(mats[2]) if len(mats) > 2 else None, code, n, s,
+                                  *sp.strides(mats[0]), int(tail_len), sp.mem_space, sp.stream, *(p(out[k]) for k in keys)))
+        return out
 
-            mats = [x, log_weights] + ([log_ratios] if log_ratios is not None else [])
-            if any((not _is_torch_tensor(m)) or m.shape != x.shape or m.dim() != 2 for m in mats):
-                raise ValueError("x, log_weights and log_ratios must be 2-D CUDA tensors of one shape")
-            dt = torch.float64 if any(m.dtype == torch.float64 for m in mats) else torch.float32
-            mats = [m.to(dt) for m in mats]
-            if any(m.stride() != mats[0].stride() for m in mats) or mats[0].stride(1) <= 0:
-                mats = [m.contiguous() for m in mats]
-            t = mats[0]
-            n, s = t.shape
-            out = {k: torch.empty(n, dtype=torch.float64, device=t.device) for k in ("mean", "var", "k_mean", "k_var", "k_none")}
-            code = _capi.PLA_F64 if dt == torch.float64 else _capi.PLA_F32
-            p = lambda m: C.c_void_p(m.data_ptr())  # noqa: E731
-            check(self._lib.pla_e_loo(self._h, p(mats[0]), p(mats[1]), p(mats[2]) if len(mats) > 2 else None, code, n, s,
-                                      t.stride(0), t.stride(1), int(tail_len), PLA_DEVICE, self._stream(),
-                                      *(p(out[k]) for k in ("mean", "var", "k_mean", "k_var", "k_none"))))
-            return out
-        mats = [np.asarray(x), np.asarray(log_weights)] + ([np.asarray(log_ratios)] if log_ratios is not None else [])
-        if any(m.ndim != 2 or m.shape != mats[0].shape for m in mats):
-            raise ValueError("x, log_weights and log_ratios must be 2-D arrays of one shape")
-        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
-        mats = [np.ascontiguousarray(m, dtype=dt) for m in mats]
-        n, s = mats[0].shape
-        out = {k: np.empty(n) for k in ("mean", "var", "k_mean", "k_var", "k_none")}
-        p = lambda m: m.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_e_loo(self._h, p(mats[0]), p(mats[1]), p(mats[2]) if len(mats) > 2 else None, dtype_code(dt), n, s,
-                                  s, 1, int(tail_len), PLA_HOST, None,
-                                  *(p(out[k]) for k in ("mean", "var", "k_mean", "k_var", "k_none"))))
+    def e_loo_quantiles(self, x, log_weights, probs):
+        """(n_obs, n_draws) draws + log-weights, quantile levels -> (n_obs, n_probs) weighted quantiles (``pla_e_loo_quantiles``:
+        e_loo.py:468-515, 534-554)."""
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        sp, mats, code, n, s = self._promoted([x, log_weights], "x and log_weights", own_strides=False)
+        out = sp.new((n, pr.size))
+        p = sp.ptr
+        check(self._lib.pla_e_loo_quantiles(self._h, p(mats[0]), p(mats[1]), code, n, s, *sp.strides(mats[0]), p(pr), pr.size,
+                                            sp.mem_space, sp.stream, p(out)))
         return out
 
     # ------------------------------------------------------------------ LOO-PIT
@@ -794,45 +808,15 @@ class Engine:
         if kind not in ("loglik", "log_weights"):
             raise ValueError(f"kind must be 'loglik' or 'log_weights', got {kind!r}")
         kcode = _capi.PLA_PIT_LOGLIK if kind == "loglik" else _capi.PLA_PIT_LOG_WEIGHTS
-        if _is_torch_tensor(mat):
-            import torch
-
-            if not _is_torch_tensor(y_hat) or mat.dim() != 2 or y_hat.shape != mat.shape or not mat.is_cuda or not y_hat.is_cuda:
-                raise ValueError("mat and y_hat must be 2-D CUDA tensors of one shape")
-            dt = torch.float64 if torch.float64 in (mat.dtype, y_hat.dtype) else torch.float32
-            mats = [m.to(dt) for m in (mat, y_hat)]
-            mats = [m if min(m.stride()) > 0 else m.contiguous() for m in mats]
-            n, s = mats[0].shape
-            dev = mats[0].device
-            yv = torch.as_tensor(y, device=dev).to(torch.float64).reshape(-1).contiguous()
-            if yv.numel() != n:
-                raise ValueError(f"y has {yv.numel()} values for {n} observations")
-            pit_le, pit_lt = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
-            diag = torch.empty(n, dtype=torch.float64, device=dev) if kind == "loglik" else None
-            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
-            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-            code = _capi.PLA_F64 if dt == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_loo_pit(self._h, p(mats[0]), p(mats[1]), p(yv), code, n, s, mats[0].stride(0), mats[0].stride(1),
-                                        mats[1].stride(0), mats[1].stride(1), kcode, mcode, int(tail_count), PLA_DEVICE, self._stream(),
-                                        p(pit_le), p(pit_lt), p(diag), p(nrep)))
-            return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": nrep}
-        mats = [np.asarray(mat), np.asarray(y_hat)]
-        if mats[0].ndim != 2 or mats[1].shape != mats[0].shape:
-            raise ValueError("mat and y_hat must be 2-D arrays of one shape")
-        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
-        mats = [self._as_2d_host(m if m.dtype == dt else m.astype(dt), allow_obs_fastest=True) for m in mats]
-        n, s = mats[0].shape
-        yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
-        if yv.size != n:
-            raise ValueError(f"y has {yv.size} values for {n} observations")
-        (so, sd), (yso, ysd) = self._host_strides(mats[0]), self._host_strides(mats[1])
-        pit_le, pit_lt = np.empty(n), np.empty(n)
-        diag = np.empty(n) if kind == "loglik" else None
-        nrep = C.c_int64(0)
-        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_loo_pit(self._h, p(mats[0]), p(mats[1]), p(yv), dtype_code(dt), n, s, so, sd, yso, ysd, kcode, mcode,
-                                    int(tail_count), PLA_HOST, None, p(pit_le), p(pit_lt), p(diag), C.byref(nrep)))
-        return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": int(nrep.value)}
+        sp, mats, code, n, s = self._promoted([mat, y_hat], "mat and y_hat", own_strides=True, host_obs=True)
+        yv = sp.vector(y, n, "y has {got} values for {n} observations")
+        pit_le, pit_lt = sp.new(n), sp.new(n)
+        diag = sp.new(n) if kind == "loglik" else None
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_loo_pit(self._h, p(mats[0]), p(mats[1]), p(yv), code, n, s, *sp.strides(mats[0]), *sp.strides(mats[1]),
+                                    kcode, mcode, int(tail_count), sp.mem_space, sp.stream, p(pit_le), p(pit_lt), p(diag), p(nrep)))
+        return {"pit_le": pit_le, "pit_lt": pit_lt, "diag": diag, "n_replaced": sp.read(nrep)}
 
     # ------------------------------------------------------------------ LOO diagnostics
     def loo_diag(self, ll, tail_count=0, method="psis", rows=None):
@@ -841,69 +825,25 @@ class Engine:
         weights and the log-scale variance of the estimate, per observation.  ``rows``: optional observation indices, one output
         entry per index.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out, nothing synchronised."""
         mcode = METHOD_CODES[method]
-        if _is_torch_tensor(ll):
-            import torch
-
-            if ll.dim() != 2 or not ll.is_cuda:
-                raise ValueError("expected a 2-D CUDA tensor")
-            if ll.dtype not in (torch.float64, torch.float32):
-                raise TypeError(f"unsupported dtype {ll.dtype}")
-            t = self._library_layout(ll)
-            n, s = t.shape
-            dev = t.device
-            idx = None if rows is None else self._device_rows(rows, n, dev)
-            m = n if idx is None else idx.numel()
-            out = [torch.empty(m, dtype=torch.float64, device=dev) for _ in range(4)]
-            nrep = torch.zeros(1, dtype=torch.int64, device=dev)
-            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            so = t.stride(0) if n > 1 else max(s, 1)
-            check(self._lib.pla_loo_diag(self._h, p(t), code, n, s, so, t.stride(1), p(idx), m, mcode, int(tail_count), PLA_DEVICE,
-                                         self._stream(), p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nrep)))
-            return {"diag": out[0], "elpd_i": out[1], "ess_w": out[2], "var_log": out[3], "n_replaced": nrep}
-        a = self._as_2d_host(ll, allow_obs_fastest=rows is None)
-        n, s = a.shape
-        so, sd = self._host_strides(a)
-        idx = None if rows is None else self._host_rows(rows, n)
-        m = n if idx is None else idx.size
-        out = [np.empty(m) for _ in range(4)]
-        nrep = C.c_int64(0)
-        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_loo_diag(self._h, p(a), dtype_code(a.dtype), n, s, so, sd, p(idx), m, mcode, int(tail_count), PLA_HOST, None,
-                                     p(out[0]), p(out[1]), p(out[2]), p(out[3]), C.byref(nrep)))
-        return {"diag": out[0], "elpd_i": out[1], "ess_w": out[2], "var_log": out[3], "n_replaced": int(nrep.value)}
+        sp, a, dims = self._matrix(ll, _LOO_DIAG, rows)
+        idx = None if rows is None else sp.rows(rows, dims[1])
+        m = dims[1] if idx is None else len(idx)
+        out = [sp.new(m) for _ in range(4)]
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_loo_diag(self._h, p(a), *dims, p(idx), m, mcode, int(tail_count), sp.mem_space, sp.stream,
+                                     p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nrep)))
+        return {"diag": out[0], "elpd_i": out[1], "ess_w": out[2], "var_log": out[3], "n_replaced": sp.read(nrep)}
 
     def loo_diag_weights(self, lw, ll):
         """Log weights of any normalisation and the log-likelihood, two (n_obs, n_draws) matrices -> ``dict(elpd_i, ess_w, var_log)``
         (``pla_loo_diag_weights``).  The matrices are promoted to one dtype (f64 if either is) and passed with their own strides.
         NumPy in -> NumPy out; CUDA tensors in -> CUDA tensors out, nothing synchronised."""
-        if _is_torch_tensor(lw):
-            import torch
-
-            if not _is_torch_tensor(ll) or lw.dim() != 2 or ll.shape != lw.shape or not lw.is_cuda or not ll.is_cuda:
-                raise ValueError("lw and ll must be 2-D CUDA tensors of one shape")
-            dt = torch.float64 if torch.float64 in (lw.dtype, ll.dtype) else torch.float32
-            mats = [m.to(dt) for m in (lw, ll)]
-            mats = [m if min(m.stride()) > 0 else m.contiguous() for m in mats]
-            n, s = mats[0].shape
-            out = [torch.empty(n, dtype=torch.float64, device=mats[0].device) for _ in range(3)]
-            p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
-            code = _capi.PLA_F64 if dt == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_loo_diag_weights(self._h, p(mats[0]), p(mats[1]), code, n, s, mats[0].stride(0), mats[0].stride(1),
-                                                 mats[1].stride(0), mats[1].stride(1), PLA_DEVICE, self._stream(), p(out[0]), p(out[1]),
-                                                 p(out[2])))
-            return {"elpd_i": out[0], "ess_w": out[1], "var_log": out[2]}
-        mats = [np.asarray(lw), np.asarray(ll)]
-        if mats[0].ndim != 2 or mats[1].shape != mats[0].shape:
-            raise ValueError("lw and ll must be 2-D arrays of one shape")
-        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
-        mats = [self._as_2d_host(m if m.dtype == dt else m.astype(dt)) for m in mats]
-        n, s = mats[0].shape
-        out = [np.empty(n) for _ in range(3)]
-        p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        so = [m.strides[0] // m.itemsize if n > 1 else s for m in mats]
-        check(self._lib.pla_loo_diag_weights(self._h, p(mats[0]), p(mats[1]), dtype_code(dt), n, s, so[0], 1, so[1], 1, PLA_HOST, None,
-                                             p(out[0]), p(out[1]), p(out[2])))
+        sp, mats, code, n, s = self._promoted([lw, ll], "lw and ll", own_strides=True)
+        out = [sp.new(n) for _ in range(3)]
+        p = sp.ptr
+        check(self._lib.pla_loo_diag_weights(self._h, p(mats[0]), p(mats[1]), code, n, s, *sp.strides(mats[0]), *sp.strides(mats[1]),
+                                             sp.mem_space, sp.stream, p(out[0]), p(out[1]), p(out[2])))
         return {"elpd_i": out[0], "ess_w": out[1], "var_log": out[2]}
 
     # ------------------------------------------------------------------ LOO influence
@@ -924,74 +864,30 @@ class Engine:
             raise ValueError("rows= needs kind='loglik'")
         args = _capi.InfluenceArgs(engine=self._h.value, kind=_capi.PLA_PIT_LOGLIK if loglik else _capi.PLA_PIT_LOG_WEIGHTS, method=mcode,
                                    tail_count=int(tail_count))
-        if _is_torch_tensor(mat):
-            import torch
-
-            if mat.dim() != 2 or not mat.is_cuda:
-                raise ValueError("expected a 2-D CUDA tensor")
-            if mat.dtype not in (torch.float64, torch.float32):
-                raise TypeError(f"unsupported dtype {mat.dtype}")
-            t = self._library_layout(mat) if loglik else (mat if min(mat.stride()) > 0 else mat.contiguous())
-            n, s = t.shape
-            dev = t.device
-            th = torch.as_tensor(theta, device=dev).to(torch.float64)
-            th = th.reshape(-1, 1) if th.dim() == 1 else th
-            if th.dim() != 2 or th.shape[0] != s:
-                raise ValueError(f"theta must be (n_draws, P) with n_draws = {s}, got {tuple(th.shape)}")
-            if min(th.stride()) <= 0:
-                th = th.contiguous()
-            nq = th.shape[1]
-            cv, sv = (torch.as_tensor(v, device=dev).to(torch.float64).reshape(-1).contiguous() for v in (center, scale))
-            if cv.numel() != nq or sv.numel() != nq:
-                raise ValueError(f"center and scale need {nq} values")
-            idx = None if rows is None else self._device_rows(rows, n, dev)
-            m = n if idx is None else idx.numel()
-            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
-            out = {"shift": new(m, nq), "m2": new(m, nq), "kl": new(m), "ess_w": new(m), "diag": new(m) if loglik else None,
-                   "n_replaced": torch.zeros(1, dtype=torch.int64, device=dev)}
-            p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-            args.mem_space, args.stream = PLA_DEVICE, self._stream().value
-            args.dtype = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            args.stride_obs, args.stride_draw = (t.stride(0) if n > 1 else max(s, 1)), t.stride(1)
-            args.theta_stride_draw, args.theta_stride_quant = th.stride(0), (th.stride(1) if nq > 1 else 1)
-            keep = (t, th, cv, sv, idx)
-        else:
-            t = self._as_2d_host(mat, allow_obs_fastest=loglik and rows is None)
-            n, s = t.shape
-            th = np.asarray(theta, dtype=np.float64)
-            th = th.reshape(-1, 1) if th.ndim == 1 else th
-            if th.ndim != 2 or th.shape[0] != s:
-                raise ValueError(f"theta must be (n_draws, P) with n_draws = {s}, got {th.shape}")
-            nq = th.shape[1]
-            if th.flags.c_contiguous:
-                std, stq = nq, 1
-            elif th.T.flags.c_contiguous:  # a (P, n_draws) array seen through .T
-                std, stq = 1, s
-            else:
-                th, std, stq = np.ascontiguousarray(th), nq, 1
-            cv, sv = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (center, scale))
-            if cv.size != nq or sv.size != nq:
-                raise ValueError(f"center and scale need {nq} values")
-            idx = None if rows is None else self._host_rows(rows, n)
-            m = n if idx is None else idx.size
-            nrep = np.zeros(1, dtype=np.int64)
-            out = {"shift": np.empty((m, nq)), "m2": np.empty((m, nq)), "kl": np.empty(m), "ess_w": np.empty(m),
-                   "diag": np.empty(m) if loglik else None, "n_replaced": nrep}
-            p = lambda x: None if x is None else x.ctypes.data  # noqa: E731
-            args.mem_space, args.stream = PLA_HOST, None
-            args.dtype = dtype_code(t.dtype)
-            args.stride_obs, args.stride_draw = self._host_strides(t)
-            args.theta_stride_draw, args.theta_stride_quant = std, stq
-            keep = (t, th, cv, sv, idx)
+        sp, t, (args.dtype, n, s, args.stride_obs, args.stride_draw) = self._matrix(mat, _LOO_DIAG if loglik else _LOG_WEIGHTS, rows)
+        th = sp.f64(theta)
+        th = th.reshape(-1, 1) if th.ndim == 1 else th
+        if th.ndim != 2 or th.shape[0] != s:
+            raise ValueError(f"theta must be (n_draws, P) with n_draws = {s}, got {tuple(th.shape)}")
+        th, (std, stq) = sp.dense(th)
+        nq = th.shape[1]
+        cv, sv = sp.vector(center), sp.vector(scale)
+        if len(cv) != nq or len(sv) != nq:
+            raise ValueError(f"center and scale need {nq} values")
+        idx = None if rows is None else sp.rows(rows, n)
+        m = n if idx is None else len(idx)
+        out = {"shift": sp.new((m, nq)), "m2": sp.new((m, nq)), "kl": sp.new(m), "ess_w": sp.new(m),
+               "diag": sp.new(m) if loglik else None, "n_replaced": sp.counter()}
+        p = sp.ptr
+        args.mem_space, args.stream = sp.mem_space, sp.stream
+        args.theta_stride_draw, args.theta_stride_quant = std, (stq if nq > 1 else 1)
         args.mat, args.n_obs, args.n_draws = p(t), n, s
         args.row_index, args.n_rows = p(idx), m
         args.theta, args.n_quant, args.center, args.scale = p(th), nq, p(cv), p(sv)
         for k in ("shift", "m2", "kl", "ess_w", "diag", "n_replaced"):
             setattr(args, k, p(out[k]))
         check(self._lib.pla_loo_influence(C.byref(args)))
-        del keep
-        if not _is_torch_tensor(mat):
-            out["n_replaced"] = int(out["n_replaced"][0])
+        out["n_replaced"] = sp.read(out["n_replaced"])
         return out
 
     # ------------------------------------------------------------------ GLM log-likelihood generator
@@ -1016,66 +912,28 @@ class Engine:
         loo = mode == "loo"
         args = _capi.GlmArgs(engine=self._h.value, family=fam[family], mode=_capi.PLA_GLM_MODE_LOO if loo else _capi.PLA_GLM_MODE_MATRIX,
                              method=METHOD_CODES[method], tail_count=int(tail_count), scale_value=float(scale_value), good_k=float(good_k))
-        obs_vecs = {"y": y, "offset": offset, "trials": trials, "obs_const": obs_const}
-        draw_vecs = {"draw_scale": draw_scale, "draw_const": draw_const}
-        tensor = _is_torch_tensor(X)
-        if tensor:
-            import torch
-
-            if X.dim() != 2 or not X.is_cuda:
-                raise ValueError("expected a 2-D CUDA tensor X")
-            dev = X.device
-            xt = X.to(torch.float64)
-            bt = torch.as_tensor(beta, device=dev).to(torch.float64)
-            if bt.dim() != 2 or bt.shape[1] != xt.shape[1]:
-                raise ValueError(f"beta must be (n_draws, P) with P = {xt.shape[1]}, got {tuple(bt.shape)}")
-            xt, bt = (t if min(t.stride()) > 0 else t.contiguous() for t in (xt, bt))
-            n, npred = xt.shape
-            s = bt.shape[0]
-            vec = lambda v, k: None if v is None else torch.as_tensor(v, device=dev).to(torch.float64).reshape(-1).contiguous()  # noqa: E731
-            xs, bs = xt.stride(), bt.stride()
-            idx = None if rows is None else self._device_rows(rows, n, dev)
-            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
-            zeros = lambda: torch.zeros(1, dtype=torch.int64, device=dev)  # noqa: E731
-            p = lambda v: None if v is None else v.data_ptr()  # noqa: E731
-            args.mem_space, args.stream = PLA_DEVICE, self._stream().value
-        else:
-            xt = np.asarray(X, dtype=np.float64)
-            bt = np.asarray(beta, dtype=np.float64)
-            if xt.ndim != 2:
-                raise ValueError("expected a 2-D (n_obs, P) array X")
-            if bt.ndim != 2 or bt.shape[1] != xt.shape[1]:
-                raise ValueError(f"beta must be (n_draws, P) with P = {xt.shape[1]}, got {bt.shape}")
-            n, npred = xt.shape
-            s = bt.shape[0]
-
-            def dense(a):  # (rows, P) as it lies, or the .T view of a dense (P, rows) array
-                if a.flags.c_contiguous:
-                    return a, (a.shape[1], 1)
-                if a.T.flags.c_contiguous:
-                    return a, (1, a.shape[0])
-                return np.ascontiguousarray(a), (a.shape[1], 1)
-
-            (xt, xs), (bt, bs) = dense(xt), dense(bt)
-            vec = lambda v, k: None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))  # noqa: E731
-            idx = None if rows is None else self._host_rows(rows, n)
-            new = lambda *shape: np.empty(shape)  # noqa: E731
-            zeros = lambda: np.zeros(1, dtype=np.int64)  # noqa: E731
-            p = lambda v: None if v is None else v.ctypes.data  # noqa: E731
-            args.mem_space, args.stream = PLA_HOST, None
+        sp = self._space(X)
+        if sp.device is not None and (X.dim() != 2 or not X.is_cuda):
+            raise ValueError("expected a 2-D CUDA tensor X")
+        xt = sp.f64(X)
+        if xt.ndim != 2:
+            raise ValueError("expected a 2-D (n_obs, P) array X")
+        bt = sp.f64(beta)
+        if bt.ndim != 2 or bt.shape[1] != xt.shape[1]:
+            raise ValueError(f"beta must be (n_draws, P) with P = {xt.shape[1]}, got {tuple(bt.shape)}")
+        (xt, xs), (bt, bs) = sp.dense(xt), sp.dense(bt)
+        n, npred = xt.shape
+        s = bt.shape[0]
+        idx = None if rows is None else sp.rows(rows, n)
+        p = sp.ptr
+        args.mem_space, args.stream = sp.mem_space, sp.stream
         keep = [xt, bt, idx]
-        for k, v in obs_vecs.items():
-            v = vec(v, k)
-            if v is not None and len(v) != n:
-                raise ValueError(f"{k} needs {n} values, got {len(v)}")
-            keep.append(v)
-            setattr(args, k, p(v))
-        for k, v in draw_vecs.items():
-            v = vec(v, k)
-            if v is not None and len(v) != s:
-                raise ValueError(f"{k} needs {s} values, got {len(v)}")
-            keep.append(v)
-            setattr(args, k, p(v))
+        for count, vecs in ((n, {"y": y, "offset": offset, "trials": trials, "obs_const": obs_const}),
+                            (s, {"draw_scale": draw_scale, "draw_const": draw_const})):
+            for k, v in vecs.items():
+                v = sp.vector(v, count, k + " needs {n} values, got {got}")
+                keep.append(v)
+                setattr(args, k, p(v))
         m = n if idx is None else len(idx)
         args.x, args.n_obs, args.n_pred = p(xt), n, npred
         args.x_stride_obs, args.x_stride_pred = max(int(xs[0]), 1), max(int(xs[1]), 1)
@@ -1088,17 +946,10 @@ class Engine:
                 raise ValueError(f"at most {_capi.GLM_MAX_TERMS} group-level terms are supported, got {len(groups)}")
             for t, term in enumerate(groups):
                 gi, u, z = (*term, None)[:3]
-                if tensor:
-                    gi = torch.as_tensor(gi, device=dev).to(torch.int32).reshape(-1).contiguous()
-                    u = torch.as_tensor(u, device=dev).to(torch.float64)
-                    if u.dim() == 2 and min(u.stride()) <= 0:
-                        u = u.contiguous()
-                    us = u.stride() if u.dim() == 2 else None
-                else:
-                    gi = np.ascontiguousarray(np.asarray(gi).reshape(-1), dtype=np.int32)
-                    u = np.asarray(u, dtype=np.float64)
-                    u, us = dense(u) if u.ndim == 2 else (u, None)
-                z = vec(z, "z")
+                gi = sp.vector(gi, dtype="int32")
+                u = sp.f64(u)
+                u, us = sp.dense(u) if u.ndim == 2 else (u, None)
+                z = sp.vector(z)
                 if us is None or u.shape[0] != s or u.shape[1] < 1:
                     raise ValueError(f"draws of term {t} must be (n_draws, G) with n_draws = {s} and G >= 1, got {tuple(u.shape)}")
                 if len(gi) != n or (z is not None and len(z) != n):
@@ -1117,65 +968,34 @@ class Engine:
             check(self._lib.pla_glm_grouped(C.byref(grouped)))
 
         if not loo:
-            out = new(m, s)
+            out = sp.new((m, s))
             args.out, args.out_pitch = p(out), s
             run()
             del keep
             return out
-        pw = pointwise or (aggregate and tensor)
-        res = {"diag": new(m) if pw else None, "loo_i": new(m) if pw else None, "lppd_i": new(m) if pw else None,
-               "agg": new(AGG_COUNT) if aggregate else None, "n_replaced": zeros()}
+        diag, loo_i, lppd_i = _pointwise(sp, m, pointwise, aggregate)
+        res = {"diag": diag, "loo_i": loo_i, "lppd_i": lppd_i, "agg": sp.new(AGG_COUNT) if aggregate else None, "n_replaced": sp.counter()}
         for k, v in res.items():
             setattr(args, k, p(v))
         run()
         del keep
-        if not tensor:
-            res["n_replaced"] = int(res["n_replaced"][0])
+        res["n_replaced"] = sp.read(res["n_replaced"])
         return res
 
     # ------------------------------------------------------------------ leave-future-out CV
-    def _lfo_input(self, ll):
-        """(matrix, n, s, stride_obs, stride_draw, dtype code, mem_space, stream, device or None).  A CUDA tensor with the draws or
-        the observations contiguous is read in place (any other strides: a contiguous copy); a host array in the same two layouts."""
-        if _is_torch_tensor(ll):
-            import torch
-
-            if ll.dim() != 2 or not ll.is_cuda:
-                raise ValueError("expected a 2-D CUDA tensor")
-            if ll.dtype not in (torch.float64, torch.float32):
-                raise TypeError(f"unsupported dtype {ll.dtype}")
-            t = self._library_layout(ll)
-            if t.shape[1] > 1 and t.stride(1) == 1 and t.shape[0] > 1 and t.stride(0) < t.shape[1]:
-                t = t.contiguous()  # (rows that overlap: an expanded tensor)
-            code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
-            so = t.stride(0) if t.shape[0] > 1 else t.shape[1]
-            return t, t.shape[0], t.shape[1], so, t.stride(1), code, PLA_DEVICE, self._stream(), t.device
-        a = self._as_2d_host(ll, allow_obs_fastest=True)
-        so, sd = self._host_strides(a)
-        return a, a.shape[0], a.shape[1], so, sd, dtype_code(a.dtype), PLA_HOST, None, None
-
     def lfo_ratios(self, ll, first, n_steps):
         """Log ratios of leave-future-out CV (``pla_lfo_ratios``): ``dict(ratios, n_replaced)`` with ``ratios[j, s]`` the sum of rows
         ``first .. first + j - 1`` of the (n_obs, n_draws) log-likelihood ``ll``, always float64, in the summation order
         include/pyloo_amd.h documents.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out, nothing synchronised."""
-        a, n, s, so, sd, code, space, stream, device = self._lfo_input(ll)
+        sp, a, dims = self._matrix(ll, _LFO)
         first, n_steps = int(first), int(n_steps)
         if n_steps < 1:
             raise ValueError("n_steps must be at least 1")
-        if device is None:
-            out = np.empty((n_steps, s))
-        else:
-            import torch
-
-            out = torch.empty((n_steps, s), dtype=torch.float64, device=device)
-        p = self._mixis_ptr
-        if device is None:
-            nrep = C.c_int64(0)
-            check(self._lib.pla_lfo_ratios(self._h, p(a), code, n, s, so, sd, first, n_steps, space, stream, p(out), C.byref(nrep)))
-            return {"ratios": out, "n_replaced": int(nrep.value)}
-        nrep = self._mixis_new(1, device, "int64")
-        check(self._lib.pla_lfo_ratios(self._h, p(a), code, n, s, so, sd, first, n_steps, space, stream, p(out), p(nrep)))
-        return {"ratios": out, "n_replaced": nrep}
+        out = sp.new((n_steps, dims[2]))
+        nrep = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_lfo_ratios(self._h, p(a), *dims, first, n_steps, sp.mem_space, sp.stream, p(out), p(nrep)))
+        return {"ratios": out, "n_replaced": sp.read(nrep)}
 
     def lfo(self, ll, first, n_steps, horizon=1, tail_count=0, k_threshold=0.7, method="psis", mode="forward"):
         """One pass of PSIS leave-future-out CV over the steps ``first .. first + n_steps - 1`` of one fit (``pla_lfo``):
@@ -1189,21 +1009,16 @@ class Engine:
         if mode not in ("forward", "backward"):
             raise ValueError(f"mode must be 'forward' or 'backward', got {mode!r}")
         mcode = METHOD_CODES[method] | (_capi.PLA_LFO_BACKWARD if mode == "backward" else 0)
-        a, n, s, so, sd, code, space, stream, device = self._lfo_input(ll)
+        sp, a, dims = self._matrix(ll, _LFO)
         first, n_steps, horizon = int(first), int(n_steps), int(horizon)
         if n_steps < 1:
             raise ValueError("n_steps must be at least 1")
-        diag, elpd = self._mixis_new(n_steps, device), self._mixis_new(n_steps, device)
-        p = self._mixis_ptr
-        if device is None:
-            high, nrep = C.c_int64(0), C.c_int64(0)
-            check(self._lib.pla_lfo(self._h, p(a), code, n, s, so, sd, first, n_steps, horizon, mcode, int(tail_count), float(k_threshold),
-                                    space, stream, p(diag), p(elpd), C.byref(high), C.byref(nrep)))
-            return {"diag": diag, "elpd_i": elpd, "first_high": int(high.value), "n_replaced": int(nrep.value)}
-        high, nrep = self._mixis_new(1, device, "int64"), self._mixis_new(1, device, "int64")
-        check(self._lib.pla_lfo(self._h, p(a), code, n, s, so, sd, first, n_steps, horizon, mcode, int(tail_count), float(k_threshold),
-                                space, stream, p(diag), p(elpd), p(high), p(nrep)))
-        return {"diag": diag, "elpd_i": elpd, "first_high": high, "n_replaced": nrep}
+        diag, elpd = sp.new(n_steps, zero=True), sp.new(n_steps, zero=True)
+        high, nrep = sp.counter(), sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_lfo(self._h, p(a), *dims, first, n_steps, horizon, mcode, int(tail_count), float(k_threshold),
+                                sp.mem_space, sp.stream, p(diag), p(elpd), p(high), p(nrep)))
+        return {"diag": diag, "elpd_i": elpd, "first_high": sp.read(high), "n_replaced": sp.read(nrep)}
 
     # ------------------------------------------------------------------ relative MCMC efficiency
     def relative_eff(self, x, n_chains=1, log=True, split=False, cap=True):
@@ -1211,17 +1026,13 @@ class Engine:
         (``pla_relative_eff``): ``dict(r_eff, n_invalid)``.  Invalid rows (NaN or +inf entries, constant rows) give NaN and are
         counted.  NumPy in -> NumPy out (and an int); CUDA tensor in -> CUDA tensors out (``n_invalid`` one int64), nothing
         synchronised."""
-        a, n, s, so, sd, code, space, stream, device = self._lfo_input(x)
+        sp, a, dims = self._matrix(x, _LFO)
         flags = (_capi.PLA_ESS_LOG if log else 0) | (_capi.PLA_ESS_SPLIT if split else 0) | (_capi.PLA_ESS_CAP if cap else 0)
-        r = self._mixis_new(n, device)
-        p = self._mixis_ptr
-        if device is None:
-            ninv = C.c_int64(0)
-            check(self._lib.pla_relative_eff(self._h, p(a), code, n, s, so, sd, int(n_chains), flags, space, stream, p(r), C.byref(ninv)))
-            return {"r_eff": r, "n_invalid": int(ninv.value)}
-        ninv = self._mixis_new(1, device, "int64")
-        check(self._lib.pla_relative_eff(self._h, p(a), code, n, s, so, sd, int(n_chains), flags, space, stream, p(r), p(ninv)))
-        return {"r_eff": r, "n_invalid": ninv}
+        r = sp.new(dims[1], zero=True)
+        ninv = sp.counter()
+        p = sp.ptr
+        check(self._lib.pla_relative_eff(self._h, p(a), *dims, int(n_chains), flags, sp.mem_space, sp.stream, p(r), p(ninv)))
+        return {"r_eff": r, "n_invalid": sp.read(ninv)}
 
     def set_ess_grid(self, max_workgroups):
         """Cap the workgroups per launch of the relative-efficiency pass (0: the library's choice); the results do not depend on it."""
@@ -1232,46 +1043,12 @@ class Engine:
         """Analysed draws per row up to which the relative-efficiency pass keeps the row on chip (``pla_ess_lds_max_draws``)."""
         return load_library().pla_ess_lds_max_draws()
 
-    def e_loo_quantiles(self, x, log_weights, probs):
-        """(n_obs, n_draws) draws + log-weights, quantile levels -> (n_obs, n_probs) weighted quantiles (``pla_e_loo_quantiles``:
-        e_loo.py:468-515, 534-554)."""
-        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        if _is_torch_tensor(x):
-            import torch
-
-            mats = [x, log_weights]
-            if any((not _is_torch_tensor(m)) or m.shape != x.shape or m.dim() != 2 for m in mats):
-                raise ValueError("x and log_weights must be 2-D CUDA tensors of one shape")
-            dt = torch.float64 if any(m.dtype == torch.float64 for m in mats) else torch.float32
-            mats = [m.to(dt) for m in mats]
-            if mats[0].stride() != mats[1].stride() or mats[0].stride(1) <= 0:
-                mats = [m.contiguous() for m in mats]
-            t = mats[0]
-            n, s = t.shape
-            out = torch.empty((n, pr.size), dtype=torch.float64, device=t.device)
-            code = _capi.PLA_F64 if dt == torch.float64 else _capi.PLA_F32
-            check(self._lib.pla_e_loo_quantiles(self._h, C.c_void_p(mats[0].data_ptr()), C.c_void_p(mats[1].data_ptr()), code, n, s,
-                                                t.stride(0), t.stride(1), pr.ctypes.data_as(C.c_void_p), pr.size, PLA_DEVICE,
-                                                self._stream(), C.c_void_p(out.data_ptr())))
-            return out
-        mats = [np.asarray(x), np.asarray(log_weights)]
-        if any(m.ndim != 2 or m.shape != mats[0].shape for m in mats):
-            raise ValueError("x and log_weights must be 2-D arrays of one shape")
-        dt = np.float32 if all(m.dtype == np.float32 for m in mats) else np.float64
-        mats = [np.ascontiguousarray(m, dtype=dt) for m in mats]
-        n, s = mats[0].shape
-        out = np.empty((n, pr.size))
-        check(self._lib.pla_e_loo_quantiles(self._h, mats[0].ctypes.data_as(C.c_void_p), mats[1].ctypes.data_as(C.c_void_p),
-                                            dtype_code(dt), n, s, s, 1, pr.ctypes.data_as(C.c_void_p), pr.size, PLA_HOST, None,
-                                            out.ctypes.data_as(C.c_void_p)))
-        return out
-
     # ------------------------------------------------------------------ model comparison
-    @staticmethod
-    def _compare_input(x):
-        """(matrix, pointer, dtype code, K, N, pitch, mem_space) of a (n_models, n_obs) matrix: rows with unit stride, a pitch
-        of at least n_obs (copied otherwise)."""
-        if _is_torch_tensor(x):
+    def _compare_input(self, x):
+        """``(space, matrix, (dtype code, K, N, pitch))`` of a (n_models, n_obs) matrix: rows with unit stride, a pitch of at least
+        n_obs (copied otherwise)."""
+        sp = self._space(x)
+        if sp.device is not None:
             import torch
 
             if x.dim() != 2 or not x.is_cuda:
@@ -1281,8 +1058,7 @@ class Engine:
             K, N = x.shape
             if (N > 1 and x.stride(1) != 1) or (K > 1 and x.stride(0) < N):
                 x = x.contiguous()
-            code = _capi.PLA_F64 if x.dtype == torch.float64 else _capi.PLA_F32
-            return x, C.c_void_p(x.data_ptr()), code, K, N, (x.stride(0) if K > 1 else N), PLA_DEVICE
+            return sp, x, (_code(x), K, N, (x.stride(0) if K > 1 else N))
         a = np.asarray(x)
         if a.dtype not in (np.float64, np.float32):
             a = a.astype(np.float64)
@@ -1291,59 +1067,45 @@ class Engine:
         K, N = a.shape
         if (N > 1 and a.strides[1] != a.itemsize) or (K > 1 and (a.strides[0] % a.itemsize or a.strides[0] < N * a.itemsize)):
             a = np.ascontiguousarray(a)
-        return a, a.ctypes.data_as(C.c_void_p), dtype_code(a.dtype), K, N, (a.strides[0] // a.itemsize if K > 1 else N), PLA_HOST
+        return sp, a, (_code(a), K, N, (a.strides[0] // a.itemsize if K > 1 else N))
 
     def compare_moments(self, x, best):
         """(n_models, n_obs) pointwise values -> ``out[3K + 1]`` (``pla_compare_moments``): ``out[3k]`` = sum of row k,
         ``out[3k + 1]`` / ``out[3k + 2]`` = mean / M2 of ``x[k] - x[best]`` (dse = sqrt(M2)), ``out[3K]`` = sum of the column
         maxima.  NumPy in -> ndarray; CUDA tensor in -> CUDA tensor (nothing synchronised)."""
-        x, ptr, code, K, N, pitch, mem = self._compare_input(x)
-        if mem == PLA_DEVICE:
-            import torch
-
-            out = torch.empty(3 * K + 1, dtype=torch.float64, device=x.device)
-            check(self._lib.pla_compare_moments(self._h, ptr, code, K, N, pitch, int(best), PLA_DEVICE, self._stream(),
-                                                C.c_void_p(out.data_ptr())))
-            return out
-        out = np.empty(3 * K + 1)
-        check(self._lib.pla_compare_moments(self._h, ptr, code, K, N, pitch, int(best), PLA_HOST, None, out.ctypes.data_as(C.c_void_p)))
+        sp, x, dims = self._compare_input(x)
+        out = sp.new(3 * dims[1] + 1)
+        check(self._lib.pla_compare_moments(self._h, sp.ptr(x), *dims, int(best), sp.mem_space, sp.stream, sp.ptr(out)))
         return out
 
     def stacking_eval(self, x, weights, scale_mul=1.0):
         """One evaluation of the stacking objective (``pla_stacking_eval``): returns ``(F, G)`` on the host, F = sum_i log d_i and
         G[k] = sum_i e_ik / d_i with e_ik = exp(s x_ik - max_k s x_ik), d_i = sum_k w_k e_ik, s = ``scale_mul``."""
-        x, ptr, code, K, N, pitch, mem = self._compare_input(x)
+        sp, x, dims = self._compare_input(x)
+        K = dims[1]
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w.size != K:
             raise ValueError(f"expected {K} weights, got {w.size}")
         out = np.empty(K + 1)
-        check(self._lib.pla_stacking_eval(self._h, ptr, code, K, N, pitch, float(scale_mul), w.ctypes.data_as(C.c_void_p), mem,
-                                          self._stream() if mem == PLA_DEVICE else None, out.ctypes.data_as(C.c_void_p)))
+        check(self._lib.pla_stacking_eval(self._h, sp.ptr(x), *dims, float(scale_mul), _ptr(w), sp.mem_space, sp.stream, _ptr(out)))
         return float(out[0]), out[1:].copy()
 
     def bb_bootstrap(self, x, n_boot, alpha=1.0, seed=0, scale_mul=1.0):
         """Bayesian-bootstrap replicates ``z`` (n_boot, n_models) of ``N * s * sum_i G_bi x_ik / sum_i G_bi`` with Gamma(alpha)
         weights drawn in the kernel from the Philox stream keyed by ``seed`` (``pla_bb_bootstrap``).  NumPy in -> ndarray;
         CUDA tensor in -> CUDA tensor (nothing synchronised)."""
-        x, ptr, code, K, N, pitch, mem = self._compare_input(x)
+        sp, x, dims = self._compare_input(x)
         B = int(n_boot)
-        if mem == PLA_DEVICE:
-            import torch
-
-            z = torch.empty((B, K), dtype=torch.float64, device=x.device)
-            check(self._lib.pla_bb_bootstrap(self._h, ptr, code, K, N, pitch, float(scale_mul), B, float(alpha), int(seed) & (2**64 - 1),
-                                             PLA_DEVICE, self._stream(), C.c_void_p(z.data_ptr())))
-            return z
-        z = np.empty((B, K))
-        check(self._lib.pla_bb_bootstrap(self._h, ptr, code, K, N, pitch, float(scale_mul), B, float(alpha), int(seed) & (2**64 - 1),
-                                         PLA_HOST, None, z.ctypes.data_as(C.c_void_p)))
+        z = sp.new((B, dims[1]))
+        check(self._lib.pla_bb_bootstrap(self._h, sp.ptr(x), *dims, float(scale_mul), B, float(alpha), int(seed) & (2**64 - 1),
+                                         sp.mem_space, sp.stream, sp.ptr(z)))
         return z
 
     def bb_gamma_draws(self, seed, alpha, n_boot, n_obs):
         """The gamma stream of :meth:`bb_bootstrap` on its own (``pla_bb_gamma_draws``): (n_boot, n_obs) ndarray of G_bi."""
         out = np.empty((int(n_boot), int(n_obs)))
         check(self._lib.pla_bb_gamma_draws(self._h, int(seed) & (2**64 - 1), float(alpha), int(n_boot), int(n_obs), PLA_HOST, None,
-                                           out.ctypes.data_as(C.c_void_p)))
+                                           _ptr(out)))
         return out
 
     def set_compare_grid(self, max_workgroups):
@@ -1361,34 +1123,26 @@ class Engine:
         (``PLA_NF_*``); CUDA tensors when any input is one (nothing synchronised), ndarrays otherwise (CPU tensors included)."""
         code = {"normal": _capi.PLA_MVN_NORMAL, "student_t": _capi.PLA_MVN_STUDENT_T}[model]
         arrays = [y, mu, mat] + ([df] if code == _capi.PLA_MVN_STUDENT_T else [])
-        if any(_is_torch_tensor(a) and a.is_cuda for a in arrays):
+        on_device = [a for a in arrays if _is_torch_tensor(a) and a.is_cuda]
+        if on_device:
             import torch
 
-            dev = next(a.device for a in arrays if _is_torch_tensor(a) and a.is_cuda)  # (CPU tensors are copied to it)
+            sp = self._space(on_device[0])  # (CPU tensors are copied to its device)
             f64 = not all(a.dtype == torch.float32 if _is_torch_tensor(a) else np.asarray(a).dtype == np.float32 for a in arrays)
             dt = torch.float64 if f64 else torch.float32
-            arrays = [(a if _is_torch_tensor(a) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=dt).contiguous() for a in arrays]
-            yt, mut, matt = arrays[:3]
-            S, N = mut.shape
-            ll = torch.empty((N, S), dtype=torch.float64, device=dev)
-            flags = torch.empty(S, dtype=torch.int32, device=dev)
-            dfp = C.c_void_p(arrays[3].data_ptr()) if len(arrays) > 3 else None
-            check(self._lib.pla_nonfactor_loglik(self._h, C.c_void_p(yt.data_ptr()), C.c_void_p(mut.data_ptr()),
-                                                 C.c_void_p(matt.data_ptr()), dfp, _capi.PLA_F64 if f64 else _capi.PLA_F32, N, S, N,
-                                                 N * N, code, PLA_DEVICE, self._stream(), C.c_void_p(ll.data_ptr()), S, 1,
-                                                 C.c_void_p(flags.data_ptr())))
-            return ll, flags
-        # host memory -- NumPy arrays and CPU tensors -- goes through the library's staging (PLA_HOST)
-        arrays = [a.detach().numpy() if _is_torch_tensor(a) else np.asarray(a) for a in arrays]
-        dt = np.float32 if all(a.dtype == np.float32 for a in arrays) else np.float64
-        arrays = [np.ascontiguousarray(a, dtype=dt) for a in arrays]
-        ya, mua, mata = arrays[:3]
-        S, N = mua.shape
-        ll = np.empty((N, S))
-        flags = np.empty(S, dtype=np.int32)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        check(self._lib.pla_nonfactor_loglik(self._h, p(ya), p(mua), p(mata), p(arrays[3]) if len(arrays) > 3 else None,
-                                             dtype_code(np.dtype(dt)), N, S, N, N * N, code, PLA_HOST, None, p(ll), S, 1, p(flags)))
+            arrays = [(a if _is_torch_tensor(a) else torch.as_tensor(np.asarray(a))).to(device=sp.device, dtype=dt).contiguous()
+                      for a in arrays]
+        else:  # host memory -- NumPy arrays and CPU tensors -- goes through the library's staging (PLA_HOST)
+            sp = _HOST
+            arrays = [a.detach().numpy() if _is_torch_tensor(a) else np.asarray(a) for a in arrays]
+            dt = np.float32 if all(a.dtype == np.float32 for a in arrays) else np.float64
+            arrays = [np.ascontiguousarray(a, dtype=dt) for a in arrays]
+        S, N = arrays[1].shape
+        ll = sp.new((N, S))
+        flags = sp.new(S, "int32")
+        p = sp.ptr
+        check(self._lib.pla_nonfactor_loglik(self._h, p(arrays[0]), p(arrays[1]), p(arrays[2]), p(arrays[3]) if len(arrays) > 3 else None,
+                                             _code(arrays[0]), N, S, N, N * N, code, sp.mem_space, sp.stream, p(ll), S, 1, p(flags)))
         return ll, flags
 
     def set_nonfactor_route(self, route):
@@ -1401,39 +1155,27 @@ class Engine:
 
     # ------------------------------------------------------------------ reductions
     def reduce_pointwise(self, diag, loo_i, lppd_i, good_k):
-        if _is_torch_tensor(loo_i):
-            import torch
-
-            agg = torch.zeros(AGG_COUNT, dtype=torch.float64, device=loo_i.device)
-            check(self._lib.pla_reduce_pointwise(self._h, C.c_void_p(diag.data_ptr()), C.c_void_p(loo_i.data_ptr()),
-                                                 C.c_void_p(lppd_i.data_ptr()), loo_i.numel(), float(good_k),
-                                                 PLA_DEVICE, self._stream(), C.c_void_p(agg.data_ptr())))
-            return agg
-        d, l, p = (np.ascontiguousarray(x, dtype=np.float64) for x in (diag, loo_i, lppd_i))
-        agg = np.zeros(AGG_COUNT)
-        check(self._lib.pla_reduce_pointwise(self._h, d.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p),
-                                             p.ctypes.data_as(C.c_void_p), l.size, float(good_k), PLA_HOST, None,
-                                             agg.ctypes.data_as(C.c_void_p)))
+        sp = self._space(loo_i)
+        if sp.device is None:
+            diag, loo_i, lppd_i = (np.ascontiguousarray(x, dtype=np.float64) for x in (diag, loo_i, lppd_i))
+        agg = sp.new(AGG_COUNT, zero=True)
+        p = sp.ptr
+        check(self._lib.pla_reduce_pointwise(self._h, p(diag), p(loo_i), p(lppd_i), len(loo_i), float(good_k), sp.mem_space, sp.stream,
+                                             p(agg)))
         return agg
 
     # ------------------------------------------------------------------ bench helpers
     def fill_synthetic(self, t, seed, row0=0, k_lo=0.05, k_hi=0.60, heavy_lo=0.0, heavy_hi=0.0):
-        import torch
-
-        code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
         n, s = t.shape
         assert t.is_contiguous()
-        check(self._lib.pla_fill_synthetic(self._h, C.c_void_p(t.data_ptr()), code, n, s, int(row0), int(seed),
+        check(self._lib.pla_fill_synthetic(self._h, _ptr(t), _code(t), n, s, int(row0), int(seed),
                                            k_lo, k_hi, heavy_lo, heavy_hi, self._stream()))
 
     def fill_synthetic_chains(self, t, seed, row0=0, chains=4, rho=0.9, offset_sd=0.3, k_lo=0.05, k_hi=0.60):
         """Rows as MCMC delivers them: chain-major stack of AR(1) chains with per-chain offsets (``pla_fill_synthetic_chains``)."""
-        import torch
-
-        code = _capi.PLA_F64 if t.dtype == torch.float64 else _capi.PLA_F32
         n, s = t.shape
         assert t.is_contiguous()
-        check(self._lib.pla_fill_synthetic_chains(self._h, C.c_void_p(t.data_ptr()), code, n, s, int(row0), int(seed), int(chains),
+        check(self._lib.pla_fill_synthetic_chains(self._h, _ptr(t), _code(t), n, s, int(row0), int(seed), int(chains),
                                                   float(rho), float(offset_sd), k_lo, k_hi, self._stream()))
 
     def set_frozen(self, on):
@@ -1473,12 +1215,11 @@ class Engine:
 
     def aggregate_pack(self, agg, rank, world, table):
         """``table`` (world x 8, this engine's device) = zeros except row ``rank`` = ``agg``: one kernel on the current stream."""
-        check(self._lib.pla_aggregate_pack(self._h, C.c_void_p(agg.data_ptr()), int(rank), int(world), C.c_void_p(table.data_ptr()),
-                                           self._stream()))
+        check(self._lib.pla_aggregate_pack(self._h, _ptr(agg), int(rank), int(world), _ptr(table), self._stream()))
 
     def aggregate_merge(self, table, world, out):
         """``out`` (8) = the per-rank aggregate rows of ``table`` merged (Chan, Golub & LeVeque): one kernel on the current stream."""
-        check(self._lib.pla_aggregate_merge(self._h, C.c_void_p(table.data_ptr()), int(world), C.c_void_p(out.data_ptr()), self._stream()))
+        check(self._lib.pla_aggregate_merge(self._h, _ptr(table), int(world), _ptr(out), self._stream()))
 
 
 def get_engine(device=None):

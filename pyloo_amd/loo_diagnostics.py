@@ -29,7 +29,7 @@ import numpy as np
 
 from .base import ISMethod, check_reff_vector, is_reff_vector, parse_method, tail_count_for
 from .e_loo import _pareto_khat_threshold
-from .engine import _is_torch_tensor, get_engine
+from .engine import _host, _is_torch_tensor, get_engine
 from .loo import bucketed_matrix, scatter_buckets
 from .relative_eff import relative_eff_from_matrix
 from .utils import get_log_likelihood, stack_samples, to_inference_data, wrap_obs
@@ -58,10 +58,6 @@ class LooDiagnostics:
     n_replaced: int
     ess: Any = None
     method: str = "psis"
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a)
 
 
 def _min_ss(k):

@@ -36,16 +36,12 @@ import numpy as np
 
 from .base import ISMethod, parse_method, tail_count_for
 from .elpd import ELPDData
-from .engine import _is_torch_tensor, get_engine
+from .engine import _host, _is_torch_tensor, get_engine
 from .loo import _scale_value
 from .rcparams import rcParams
 from .utils import get_log_likelihood, stack_samples, to_inference_data, wrap_obs
 
 __all__ = ["loo_lfo", "loo_lfo_from_matrix"]
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a)
 
 
 def _time_matrix(obj, var_name):

@@ -17,7 +17,7 @@ from typing import Any
 import numpy as np
 
 from .base import ISMethod, parse_method, tail_count_for
-from .engine import _is_torch_tensor, get_engine
+from .engine import _host, _is_torch_tensor, get_engine
 from .utils import get_log_likelihood, group_variable, stack_samples, to_inference_data, wrap_obs
 
 __all__ = ["loo_pit", "loo_pit_from_matrix", "LooPitResult"]
@@ -34,10 +34,6 @@ class LooPitResult:
     pareto_k: Any = None
     good_k: Any = None
     warning: Any = None
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a)
 
 
 def _randomize(pit_le, pit_lt, randomized, seed):
