@@ -715,6 +715,54 @@ typedef struct pla_glm_grouped_args {
 int pla_glm_grouped(const pla_glm_grouped_args *args);
 
 /*
+ * Cluster-marginal log-likelihood of a multilevel GLM, and PSIS-LOO over it: leave-one-cluster-out with the left-out cluster's own
+ * effect integrated out of the likelihood (csrc/pla_glm_marginal.h; Merkle, Furr & Rabe-Hesketh 2019).  Every observation belongs
+ * to one cluster c in [0, n_clusters); its linear predictor is eta[i, s] = rest[i, s] + z_i u with rest what pla_glm_grouped
+ * computes (x beta + offset and the conditional terms) and u | draw s ~ N(0, tau_s^2).  By quadrature on nodes of the cluster:
+ *     e[q]      = ( log_weights[c, q] + ( (-0.5 log 2 pi - log tau_s) - 0.5 (nodes[c, q] / tau_s)^2 ) )
+ *                 + sum_{i in c, in member order} ll(y_i | rest[i, s] + z_i nodes[c, q])
+ *     mll[c, s] = max_q e[q] + log sum_q exp(e[q] - max_q e[q])                 (-inf if every e[q] is -inf)
+ * ll is the density of pla_glm.  The product z_i node and every sum are rounded once; with z NULL the product is not formed.
+ * THE SUMMATION RULE.  With L = pla_glm_marginal_segment(), segment k of a cluster is its members [k L, (k + 1) L); a segment sum
+ * starts from zero and runs in member order; the segment sums are added in order of k, starting from the sum of segment 0.
+ * mll[c, s] depends on the rest values of the cluster's members in member order, on their entries of the vectors, on row c of nodes
+ * and log_weights, on tau_s and on L -- not on the grid, the block size (PLA_INGEST_BLOCK_MB), the place of the cluster in the list,
+ * its label, the position of the draw or the memory space.  There are no floating-point atomics.
+ *
+ * Set struct_size = sizeof(pla_glm_marginal_args), grouped.struct_size and grouped.glm.struct_size as pla_glm_grouped wants them.
+ *   grouped             the argument block of pla_glm_grouped: family (not PLA_GLM_LINPRED), mode, x, beta, the vectors, the terms;
+ *                       grouped.glm.row_index must be NULL.  Its output fields describe one row per CLUSTER: PLA_GLM_MODE_MATRIX
+ *                       writes the (n_clusters, n_draws) matrix mll to out; PLA_GLM_MODE_LOO runs the pass of pla_psis_loo on
+ *                       blocks of finished clusters, diag / loo_i / lppd_i are [n_clusters]; a NaN mll is replaced by -1e10 and
+ *                       counted in *n_replaced.
+ *   n_clusters, cluster_offsets [n_clusters + 1], members [n_members], n_members
+ *                       cluster c holds the observations members[cluster_offsets[c] .. cluster_offsets[c + 1]) -- the image of a
+ *                       grouping in compressed rows, the rows sorted by cluster.  Host lists are checked (offsets start at 0, do
+ *                       not decrease and end at n_members; members lie in [0, n_obs): else PLA_ERR_ARG).  A device pair of offsets
+ *                       that decreases or leaves [0, n_members] is an empty cluster, a device member is clamped into [0, n_obs).
+ *                       An empty cluster is legal: its mll is the log-sum-exp of prior plus log-weight alone.
+ *   z                   [n_obs] or NULL (1): the covariate of the integrated effect
+ *   tau                 [n_draws], positive and finite (checked on the host)
+ *   n_nodes, nodes, log_weights      1 <= n_nodes <= 32; [n_clusters][n_nodes] each
+ * A PLA_DEVICE call waits once, at its start, for the n_clusters + 1 offsets to reach the host -- the member list is cut into blocks
+ * where clusters and segments end -- and for its tables to reach the device; inside a stream capture it is PLA_ERR_UNSUPPORTED.
+ * Engine memory: one block of the linear predictor, one block of finished clusters (unless the matrix goes into a device buffer in
+ * place), 24 bytes per segment, and n_nodes (padded to 8, 16 or 32) x n_draws doubles per segment of the clusters of a block that
+ * are longer than L.
+ */
+typedef struct pla_glm_marginal_args {
+  int64_t struct_size;
+  pla_glm_grouped_args grouped;
+  int64_t n_clusters, n_members;
+  const int64_t *cluster_offsets, *members;
+  const double *z, *tau;
+  int64_t n_nodes;
+  const double *nodes, *log_weights;
+} pla_glm_marginal_args;
+int pla_glm_marginal(const pla_glm_marginal_args *args);
+int pla_glm_marginal_segment(void); /* L of the summation rule */
+
+/*
  * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
  * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
  * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):

@@ -39,6 +39,7 @@ SYMBOLS = (
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
     "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence", "pla_glm", "pla_glm_grouped",
+    "pla_glm_marginal", "pla_glm_marginal_segment",
     "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
 
@@ -111,6 +112,26 @@ class GlmGroupedArgs(C.Structure):
         super().__init__(**kw)
         self.struct_size = C.sizeof(GlmGroupedArgs)
         self.glm.struct_size = C.sizeof(GlmArgs)
+
+
+GLM_MARGINAL_MAX_NODES = 32
+
+
+class GlmMarginalArgs(C.Structure):
+    """``pla_glm_marginal_args`` of include/pyloo_amd.h: ``grouped`` is a ``GlmGroupedArgs`` (all three ``struct_size`` are set on
+    construction)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int64), ("grouped", GlmGroupedArgs), ("n_clusters", C.c_int64), ("n_members", C.c_int64),
+        ("cluster_offsets", C.c_void_p), ("members", C.c_void_p), ("z", C.c_void_p), ("tau", C.c_void_p),
+        ("n_nodes", C.c_int64), ("nodes", C.c_void_p), ("log_weights", C.c_void_p),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GlmMarginalArgs)
+        self.grouped.struct_size = C.sizeof(GlmGroupedArgs)
+        self.grouped.glm.struct_size = C.sizeof(GlmArgs)
 
 
 class EngineError(RuntimeError):
@@ -201,6 +222,8 @@ def load_library():
     lib.pla_loo_influence.argtypes = [C.POINTER(InfluenceArgs)]
     lib.pla_glm.argtypes = [C.POINTER(GlmArgs)]
     lib.pla_glm_grouped.argtypes = [C.POINTER(GlmGroupedArgs)]
+    lib.pla_glm_marginal.argtypes = [C.POINTER(GlmMarginalArgs)]
+    lib.pla_glm_marginal_segment.argtypes = []
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]

@@ -903,6 +903,21 @@ class Engine:
         ``groups``: group-level terms, a sequence of ``(index, draws)`` or ``(index, draws, z)`` -- ``index`` [n_obs] integers in
         ``[0, G)``, ``draws`` (n_draws, G) with its own strides, ``z`` [n_obs] or None (1) --, added to the linear predictor in the
         order given (``pla_glm_grouped``; an empty sequence goes through that entry with no terms, None through ``pla_glm``)."""
+        sp, args, terms, keep, m, s = self._glm_block(X, beta, family, y, offset, trials, obs_const, draw_scale, draw_const, rows, mode,
+                                                      tail_count, method, scale_value, good_k, groups)
+
+        def run():
+            if groups is None:
+                check(self._lib.pla_glm(C.byref(args)))
+            else:
+                check(self._lib.pla_glm_grouped(C.byref(self._glm_grouped(args, terms))))
+
+        return self._glm_finish(sp, args, m, s, mode == "loo", pointwise, aggregate, run, keep)
+
+    def _glm_block(self, X, beta, family, y, offset, trials, obs_const, draw_scale, draw_const, rows, mode, tail_count, method,
+                   scale_value, good_k, groups):
+        """The argument block of ``pla_glm`` without its outputs, in the memory space of ``X`` -> ``(space, block, terms, what to keep
+        alive over the call, rows of the call, n_draws)``; ``terms``: one tuple of ``pla_glm_term`` entries per term of ``groups``."""
         fam = {"linpred": _capi.PLA_GLM_LINPRED, "gaussian": _capi.PLA_GLM_GAUSSIAN, "binomial": _capi.PLA_GLM_BINOMIAL_LOGIT,
                "poisson": _capi.PLA_GLM_POISSON_LOG}
         if family not in fam:
@@ -957,16 +972,20 @@ class Engine:
                 keep += [gi, u, z]
                 terms.append((p(gi), p(z), p(u), max(int(us[0]), 1), max(int(us[1]), 1), int(u.shape[1])))
 
-        def run():
-            if groups is None:
-                check(self._lib.pla_glm(C.byref(args)))
-                return
-            grouped = _capi.GlmGroupedArgs(n_terms=len(terms))
-            grouped.glm = args
-            for t, (gp, zp, up, sd, sg, ng) in enumerate(terms):
-                grouped.terms[t] = _capi.GlmTerm(group_index=gp, z=zp, u=up, u_stride_draw=sd, u_stride_group=sg, n_groups=ng)
-            check(self._lib.pla_glm_grouped(C.byref(grouped)))
+        return sp, args, terms, keep, m, s
 
+    @staticmethod
+    def _glm_grouped(args, terms):
+        grouped = _capi.GlmGroupedArgs(n_terms=len(terms))
+        grouped.glm = args
+        for t, (gp, zp, up, sd, sg, ng) in enumerate(terms):
+            grouped.terms[t] = _capi.GlmTerm(group_index=gp, z=zp, u=up, u_stride_draw=sd, u_stride_group=sg, n_groups=ng)
+        return grouped
+
+    @staticmethod
+    def _glm_finish(sp, args, m, s, loo, pointwise, aggregate, run, keep):
+        """The outputs of a GLM call of ``m`` rows into ``args``, then ``run()``: the matrix, or the dict of the fused LOO pass."""
+        p = sp.ptr
         if not loo:
             out = sp.new((m, s))
             args.out, args.out_pitch = p(out), s
@@ -981,6 +1000,49 @@ class Engine:
         del keep
         res["n_replaced"] = sp.read(res["n_replaced"])
         return res
+
+    def glm_marginal(self, X, beta, family, index, tau, nodes, log_weights, z=None, y=None, offset=None, trials=None, obs_const=None,
+                     draw_scale=None, draw_const=None, mode="matrix", tail_count=0, method="psis", scale_value=1.0, good_k=0.7,
+                     pointwise=True, aggregate=True, groups=None):
+        """The cluster-marginal log-likelihood of a multilevel GLM (``pla_glm_marginal``): per cluster of ``index`` (a
+        :class:`~pyloo_amd.loo_group.GroupIndex` over the rows of ``X``) the likelihood of its observations with the cluster's own
+        effect ``u ~ N(0, tau_s^2)`` -- entering the linear predictor of :meth:`glm` as ``z_i u`` -- integrated out by quadrature on
+        ``nodes`` / ``log_weights`` (C, n_nodes).  ``tau`` is [n_draws], ``z`` [n_obs] or None (1); everything else is :meth:`glm`'s,
+        ``family="linpred"`` and ``rows`` excepted.  ``mode="matrix"`` returns the (C, n_draws) matrix, ``mode="loo"`` the dict of
+        the fused PSIS-LOO pass with one entry per cluster.  A CUDA ``X`` waits once for the offsets of ``index``."""
+        if family == "linpred":
+            raise ValueError("glm_marginal needs a likelihood: family must be 'gaussian', 'binomial' or 'poisson'")
+        sp, args, terms, keep, n, s = self._glm_block(X, beta, family, y, offset, trials, obs_const, draw_scale, draw_const, None, mode,
+                                                      tail_count, method, scale_value, good_k, groups)
+        n_clusters = int(index.n_groups)
+        if int(index.n_obs) != n:
+            raise ValueError(f"index covers {int(index.n_obs)} observations, X has {n} rows")
+        off, mem = sp.index(index)
+        tau = sp.vector(tau, s, "tau needs {n} values, one per draw, got {got}")
+        z = sp.vector(z, n, "z needs {n} values, got {got}")
+        nodes, log_weights = sp.f64(nodes), sp.f64(log_weights)
+        if nodes.ndim != 2 or nodes.shape[0] != n_clusters or tuple(log_weights.shape) != tuple(nodes.shape):
+            raise ValueError(f"nodes and log_weights must be (n_clusters, n_nodes) with n_clusters = {n_clusters}, got "
+                             f"{tuple(nodes.shape)} and {tuple(log_weights.shape)}")
+        n_nodes = int(nodes.shape[1])
+        if not 1 <= n_nodes <= _capi.GLM_MARGINAL_MAX_NODES:
+            raise ValueError(f"n_nodes must lie in [1, {_capi.GLM_MARGINAL_MAX_NODES}], got {n_nodes}")
+        nodes, log_weights = (a.contiguous() if sp.device is not None else np.ascontiguousarray(a) for a in (nodes, log_weights))
+        keep += [off, mem, tau, z, nodes, log_weights]
+        p = sp.ptr
+        marg = _capi.GlmMarginalArgs(n_clusters=n_clusters, n_members=n, cluster_offsets=p(off), members=p(mem), z=p(z), tau=p(tau),
+                                     n_nodes=n_nodes, nodes=p(nodes), log_weights=p(log_weights))
+
+        def run():
+            marg.grouped = self._glm_grouped(args, terms)
+            check(self._lib.pla_glm_marginal(C.byref(marg)))
+
+        return self._glm_finish(sp, args, n_clusters, s, mode == "loo", pointwise, aggregate, run, keep)
+
+    @staticmethod
+    def glm_marginal_segment():
+        """Members per segment of the summation rule of ``pla_glm_marginal`` (``pla_glm_marginal_segment``)."""
+        return load_library().pla_glm_marginal_segment()
 
     # ------------------------------------------------------------------ leave-future-out CV
     def lfo_ratios(self, ll, first, n_steps):
