@@ -125,6 +125,56 @@ def parity_matrix(n_chains, n, log, dtype=np.float64):
     return np.concatenate([ar1_rows(rng, per, n_chains, n, phi, log) for phi in FAMILIES.values()]).astype(dtype)
 
 
+# ---- rows at the two ends of Geyer's loop (tests/test_gpu_relative_eff_edges.py) ------------------------------------------------------
+def unmixed_rows(rng, n_rows, n_chains, n, log):
+    """Chains that have not mixed: AR(1) at phi = 0.5 with chain c shifted by 10 c -- z + 10 c, or -3 + 0.07 (z + 10 c) for a log row.
+    V >> W keeps rho-hat near 1, so Geyer's rule never stops: the loop walks every lag the rule allows (stop = n for even n, n - 1
+    for odd n) with margins near 1.  Needs n_chains >= 2.  Chain major like ar1_rows."""
+    assert n_chains >= 2
+    z = ar1_rows(rng, n_rows, n_chains, n, 0.5, log=False).reshape(n_rows, n_chains, n)
+    v = (z + 10.0 * np.arange(n_chains)[None, :, None]).reshape(n_rows, n_chains * n)
+    return -3.0 + 0.07 * v if log else v
+
+
+def alternating_rows(rng, n_rows, n_chains, n, log):
+    """Chains that flip sign at every draw: (+1, -1, +1, ...) times 1 + 0.01 N(0, 1) per chain, plus 1e-3 N(0, 1) per draw; a log row
+    is -3 + 0.7 times that.  rho-hat(1) <= -1, so the loop ends at once or after one pair and tau lands on its floor:
+    r_eff = log10(C n) of the analysed shape.  Chain major like ar1_rows."""
+    e = ar1_rows(rng, n_rows, n_chains, n, 0.0, log=False).reshape(n_rows, n_chains, n)
+    amp = 1.0 + 0.01 * rng.standard_normal((n_rows, n_chains, 1))
+    sign = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+    v = (sign * amp + 1e-3 * e).reshape(n_rows, n_chains * n)
+    return -3.0 + 0.7 * v if log else v
+
+
+# chains x draws at the strides of csrc/pla_ess.h, by the structure each group steps over (tests/test_gpu_relative_eff_edges.py runs
+# them with parity_matrix's rows, split as well wherever a half chain keeps four draws)
+EDGE_SHAPES = {
+    # lane l owns draws l, l + 64, ... of a chain (kWave)
+    "wave": ((1, 63), (1, 64), (1, 65), (3, 63), (3, 64), (3, 65)),
+    # the sweeps issue kEssBatch x 64 = 512 draws per step; the last three split into halves of 511 / 512 / 513
+    "sweep": ((1, 511), (1, 512), (1, 513), (2, 511), (2, 513), (1, 1023), (1, 1025), (2, 1027)),
+    # ess_load takes kEssLoadBatch x 64 = 1024 draws per step (split rows and the long route): split halves of 1025 and of 1024
+    # (the middle draw skipped), and an unsplit row of the long route
+    "load": ((1, 2050), (2, 2049), (3, 1366)),
+    # the 64 register slots of ess_fetch / ess_commit with several chains: 4096 analysed draws, 4095, and just above the limit
+    "limit": ((8, 512), (64, 64), (1024, 4), (3, 1365), (7, 585), (3, 1366), (17, 241), (1025, 4)),
+    # the route follows the analysed draws: long unsplit and on chip split; long both ways; long with split chains of 4096
+    "route": ((2, 2049), (1, 4098), (1, 8192)),
+    # the Geyer loop's bound t < n - 1 at tiny n; the last five split into halves of four or five draws
+    "tiny": ((1, 5), (1, 6), (1, 7), (2, 5), (1, 8), (1, 9), (2, 8), (3, 9), (1, 11)),
+}
+UNMIXED_SHAPES = ((2, 4), (2, 5), (2, 6), (2, 7), (3, 64), (3, 65), (2, 513), (8, 512), (3, 1366), (2, 1027))
+ALTERNATING_SHAPES = ((1, 4), (1, 5), (1, 10), (1, 64), (1, 65), (4, 250), (1, 513), (1, 4096), (1, 4097), (3, 1366))
+
+
+def loop_end_matrix(family, n_chains, n, log, dtype=np.float64):
+    """Three rows of unmixed_rows or alternating_rows for one shape, seeded like parity_matrix."""
+    make = {"unmixed": unmixed_rows, "alternating": alternating_rows}[family]
+    rng = np.random.default_rng({"unmixed": 78000, "alternating": 79000}[family] + 100 * n_chains + n + (5 if log else 0))
+    return make(rng, 3, n_chains, n, log).astype(dtype)
+
+
 class OracleEssEngine:
     """Stand-in for ``Engine.relative_eff`` on this restatement; records what the front passed."""
 
