@@ -631,7 +631,19 @@ int pla_loo_influence(const pla_influence_args *args);
  *     PLA_GLM_BINOMIAL_LOGIT   obs_const_i + y_i eta - trials_i softplus(eta)          softplus(e) = max(e, 0) + log1p(exp(-|e|));
  *                              obs_const_i = lgamma(n+1) - lgamma(y+1) - lgamma(n-y+1); trials NULL: 1 (Bernoulli), obs_const NULL: 0
  *     PLA_GLM_POISSON_LOG      obs_const_i + y_i eta - exp(eta)                        obs_const_i = -lgamma(y_i + 1)
- * The constants are the caller's.  Values that are not finite propagate by IEEE rules; in PLA_GLM_MODE_LOO a NaN log-likelihood is
+ *     PLA_GLM_NEGBINOMIAL_LOG  (((obs_const_i + draw_const_s) + lgamma(y_i + phi_s)) + y_i eta) - (y_i + phi_s) L,
+ *                              L = max(eta, lp_s) + log1p(exp(-|eta - lp_s|)), lp_s = log(phi_s) taken once per tile of draws;
+ *                              phi_s = draw_scale_s (NB2: mean exp(eta), variance mu + mu^2 / phi), draw_const_s = phi log(phi) -
+ *                              lgamma(phi), obs_const_i = -lgamma(y_i + 1)
+ *     PLA_GLM_GAMMA_LOG        (draw_const_s + (alpha_s - 1) obs_const_i) - alpha_s (eta + y_i exp(-eta))
+ *                              alpha_s = draw_scale_s (the shape; mean exp(eta)), draw_const_s = alpha log(alpha) - lgamma(alpha),
+ *                              obs_const_i = log(y_i)
+ *     PLA_GLM_BINOMIAL_PROBIT  (obs_const_i + y_i logPhi(eta)) + (trials_i - y_i) logPhi(-eta); a product whose factor y_i or
+ *                              trials_i - y_i is 0 is not formed (it is 0, not 0 * -inf); trials, obs_const as for
+ *                              PLA_GLM_BINOMIAL_LOGIT.  With h = 0.5 erfcx(|x| / sqrt 2), w = 0.5 fl(x^2) and r = x^2 - fl(x^2) (exact,
+ *                              one fused multiply-add), logPhi(x) = log(h) - w for x < 0 and log1p(-(h exp(-w)) (1 - 0.5 r))
+ *                              otherwise: finite in both tails, and the upper tail keeps its relative accuracy
+ * Every sum and product is rounded once, in the order written (no contraction).  The constants are the caller's.  Values that are not finite propagate by IEEE rules; in PLA_GLM_MODE_LOO a NaN log-likelihood is
  * replaced by -1e10 and counted (the rule of pla_psis_loo's callers).  eta[i, s] and ll[i, s] depend on row i of x, row s of beta,
  * n_pred and the vectors' entries alone -- not on the grid, the block size (PLA_INGEST_BLOCK_MB), the position of the row or the
  * draw, a row list, or the layout and strides of x and beta; there are no floating-point atomics.
@@ -648,7 +660,8 @@ int pla_loo_influence(const pla_influence_args *args);
  *                       orientation
  *   beta, n_draws, beta_stride_draw, beta_stride_pred        the same
  *   y, offset, trials, obs_const     [n_obs]; y is needed by every family but PLA_GLM_LINPRED, the other three may be NULL
- *   draw_scale, draw_const           [n_draws], PLA_GLM_GAUSSIAN only (NULL: PLA_ERR_ARG there)
+ *   draw_scale, draw_const           [n_draws]; PLA_GLM_GAUSSIAN, PLA_GLM_NEGBINOMIAL_LOG and PLA_GLM_GAMMA_LOG need both (NULL:
+ *                       PLA_ERR_ARG, with a message of its own for each of the two under the last two families); unused otherwise
  *   row_index, n_rows   optional rows of x (m = n_rows; repeats and any order allowed), else m = n_obs; a device list is clamped
  *                       into [0, n_obs), a host list out of range is PLA_ERR_ARG
  *   mem_space, stream   where EVERY pointer of the block lives; PLA_DEVICE: everything is enqueued on stream
@@ -657,6 +670,9 @@ int pla_loo_influence(const pla_influence_args *args);
 #define PLA_GLM_GAUSSIAN 1
 #define PLA_GLM_BINOMIAL_LOGIT 2
 #define PLA_GLM_POISSON_LOG 3
+#define PLA_GLM_NEGBINOMIAL_LOG 4
+#define PLA_GLM_GAMMA_LOG 5
+#define PLA_GLM_BINOMIAL_PROBIT 6
 #define PLA_GLM_MODE_MATRIX 0
 #define PLA_GLM_MODE_LOO 1
 typedef struct pla_glm_args {
@@ -730,7 +746,8 @@ int pla_glm_grouped(const pla_glm_grouped_args *args);
  * its label, the position of the draw or the memory space.  There are no floating-point atomics.
  *
  * Set struct_size = sizeof(pla_glm_marginal_args), grouped.struct_size and grouped.glm.struct_size as pla_glm_grouped wants them.
- *   grouped             the argument block of pla_glm_grouped: family (not PLA_GLM_LINPRED), mode, x, beta, the vectors, the terms;
+ *   grouped             the argument block of pla_glm_grouped: family (PLA_GLM_GAUSSIAN, PLA_GLM_BINOMIAL_LOGIT or
+ *                       PLA_GLM_POISSON_LOG; any other: PLA_ERR_ARG), mode, x, beta, the vectors, the terms;
  *                       grouped.glm.row_index must be NULL.  Its output fields describe one row per CLUSTER: PLA_GLM_MODE_MATRIX
  *                       writes the (n_clusters, n_draws) matrix mll to out; PLA_GLM_MODE_LOO runs the pass of pla_psis_loo on
  *                       blocks of finished clusters, diag / loo_i / lppd_i are [n_clusters]; a NaN mll is replaced by -1e10 and

@@ -64,6 +64,7 @@ class InfluenceArgs(C.Structure):
 
 
 PLA_GLM_LINPRED, PLA_GLM_GAUSSIAN, PLA_GLM_BINOMIAL_LOGIT, PLA_GLM_POISSON_LOG = 0, 1, 2, 3
+PLA_GLM_NEGBINOMIAL_LOG, PLA_GLM_GAMMA_LOG, PLA_GLM_BINOMIAL_PROBIT = 4, 5, 6
 PLA_GLM_MODE_MATRIX, PLA_GLM_MODE_LOO = 0, 1
 GLM_MAX_PRED = 256
 

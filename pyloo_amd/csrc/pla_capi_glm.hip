@@ -44,8 +44,7 @@ int glm_check(const pla_glm_args* a, int64_t n_terms, const pla_glm_term* terms,
   pla_engine* eng = a->engine;
   if (!eng) return fail(PLA_ERR_ARG, "engine is NULL");
   const int family = a->family, mode = a->mode, mem_space = a->mem_space;
-  if (family != PLA_GLM_LINPRED && family != PLA_GLM_GAUSSIAN && family != PLA_GLM_BINOMIAL_LOGIT && family != PLA_GLM_POISSON_LOG)
-    return fail(PLA_ERR_ARG, "bad family %d", family);
+  if (family < PLA_GLM_LINPRED || family > PLA_GLM_BINOMIAL_PROBIT) return fail(PLA_ERR_ARG, "bad family %d", family);
   if (mode != PLA_GLM_MODE_MATRIX && mode != PLA_GLM_MODE_LOO) return fail(PLA_ERR_ARG, "bad mode %d", mode);
   const bool loo = mode == PLA_GLM_MODE_LOO;
   if (loo && family == PLA_GLM_LINPRED) return fail(PLA_ERR_ARG, "PLA_GLM_MODE_LOO needs a likelihood, not PLA_GLM_LINPRED");
@@ -61,6 +60,12 @@ int glm_check(const pla_glm_args* a, int64_t n_terms, const pla_glm_term* terms,
   if (family != PLA_GLM_LINPRED && n_obs > 0 && !a->y) return fail(PLA_ERR_ARG, "y is NULL");
   if (family == PLA_GLM_GAUSSIAN && (!a->draw_scale || !a->draw_const))
     return fail(PLA_ERR_ARG, "PLA_GLM_GAUSSIAN needs draw_scale and draw_const");
+  if (family == PLA_GLM_NEGBINOMIAL_LOG || family == PLA_GLM_GAMMA_LOG) {
+    const char* name = family == PLA_GLM_GAMMA_LOG ? "PLA_GLM_GAMMA_LOG" : "PLA_GLM_NEGBINOMIAL_LOG";
+    const char* what = family == PLA_GLM_GAMMA_LOG ? "the shape alpha" : "the dispersion phi";
+    if (!a->draw_scale) return fail(PLA_ERR_ARG, "%s needs draw_scale, %s per draw", name, what);
+    if (!a->draw_const) return fail(PLA_ERR_ARG, "%s needs draw_const, a log(a) - lgamma(a) of draw_scale per draw", name);
+  }
   if (loo) {
     if (a->method != PLA_PSIS && a->method != PLA_SIS && a->method != PLA_TIS) return fail(PLA_ERR_ARG, "bad method");
     if (a->method == PLA_PSIS) {
@@ -202,7 +207,7 @@ int glm_prepare(const pla_glm_args* a, int family, int64_t n_terms, const pla_gl
   g.n_draws = S;
   g.y = in.y;
   g.offset = in.offset;
-  g.trials = family == PLA_GLM_BINOMIAL_LOGIT ? in.trials : nullptr;
+  g.trials = family == PLA_GLM_BINOMIAL_LOGIT || family == PLA_GLM_BINOMIAL_PROBIT ? in.trials : nullptr;
   g.obs_const = in.obs_const;
   g.sigma = in.sigma;
   g.draw_const = in.draw_const;
@@ -391,6 +396,10 @@ void marg_plan(const std::vector<int64_t>& lo, const std::vector<int64_t>& hi, i
 
 int marg_run(const pla_glm_marginal_args* a) {
   const pla_glm_args* ga = &a->grouped.glm;
+  if (ga->family == PLA_GLM_NEGBINOMIAL_LOG || ga->family == PLA_GLM_GAMMA_LOG || ga->family == PLA_GLM_BINOMIAL_PROBIT)
+    return fail(PLA_ERR_ARG, "pla_glm_marginal takes PLA_GLM_GAUSSIAN, PLA_GLM_BINOMIAL_LOGIT and PLA_GLM_POISSON_LOG, not %s",
+                ga->family == PLA_GLM_NEGBINOMIAL_LOG ? "PLA_GLM_NEGBINOMIAL_LOG" : ga->family == PLA_GLM_GAMMA_LOG ? "PLA_GLM_GAMMA_LOG"
+                                                                                                                  : "PLA_GLM_BINOMIAL_PROBIT");
   int rc = glm_check(ga, a->grouped.n_terms, a->grouped.terms, nullptr, 0, a->n_clusters);
   if (rc) return rc;
   pla_engine* eng = ga->engine;

@@ -5,6 +5,12 @@
 //     PLA_GLM_GAUSSIAN         draw_const_s - 0.5 ((y_i - eta) / sigma_s)^2            (a division)
 //     PLA_GLM_BINOMIAL_LOGIT   obs_const_i + y_i eta - trials_i softplus(eta),  softplus(e) = max(e, 0) + log1p(exp(-|e|))
 //     PLA_GLM_POISSON_LOG      obs_const_i + y_i eta - exp(eta)
+//     PLA_GLM_NEGBINOMIAL_LOG  (((obs_const_i + draw_const_s) + lgamma(y_i + phi_s)) + y_i eta) - (y_i + phi_s) L,
+//                              L = max(eta, lp_s) + log1p(exp(-|eta - lp_s|)), phi_s = sigma_s, lp_s = log(phi_s) once per tile of draws
+//     PLA_GLM_GAMMA_LOG        (draw_const_s + (alpha_s - 1) obs_const_i) - alpha_s (eta + y_i exp(-eta)),  alpha_s = sigma_s
+//     PLA_GLM_BINOMIAL_PROBIT  (obs_const_i + y_i logPhi(eta)) + (trials_i - y_i) logPhi(-eta), a product with a zero factor not formed;
+//                              glm_log_ndtr_pair: with h = 0.5 erfcx(|e| / sqrt 2), w = 0.5 fl(e^2), r = e^2 - fl(e^2): logPhi(-|e|) = log(h) - w, logPhi(|e|) = log1p(-(h exp(-w)) (1 - 0.5 r))
+// (the last three are instantiated in pla_k_glm_families.hip and pla_k_glm_terms_families.hip; lgamma and erfcx are the device library's)
 // offset, trials and obs_const may be null (0, 1, 0).  Values that are not finite propagate by IEEE rules; with a counter given
 // (the LOO route) a NaN result is stored as -1e10 and counted (loo.py:218-227).
 //
@@ -63,7 +69,7 @@ struct GlmParams {
   const double* zero;  // a 0.0 (the slot behind bimg)
   int s_pad, p_pad, n_pred, n_draws;
   const double *y, *offset, *trials, *obs_const;  // [n_src]; the last three may be null
-  const double *sigma, *draw_const;               // [n_draws], PLA_GLM_GAUSSIAN
+  const double *sigma, *draw_const;               // [n_draws], the families of glm_draw_values
   double* out;                                    // (n_rows, n_draws) with row pitch `pitch`, draws fastest
   int64_t pitch;
   unsigned long long* replaced;  // non-null: NaN -> -1e10, counted here
@@ -72,6 +78,13 @@ struct GlmParams {
 
 // the kernel's parameters of a launch and its grid (pla_k_glm.hip; shared with the flavour with group-level terms, pla_glm_terms.h)
 unsigned glm_fill_params(const GlmLaunch& g, GlmParams* out);
+// the families pla_k_glm.hip does not instantiate (pla_k_glm_families.hip); *name: the family as the route text names it
+hipError_t launch_glm_more(int family, const GlmParams& p, unsigned grid, hipStream_t stream, const char** name);
+
+// what a family reads: a scale and a constant per draw; trials per observation; a constant per observation
+constexpr bool glm_draw_values(int fam) { return fam == PLA_GLM_GAUSSIAN || fam == PLA_GLM_NEGBINOMIAL_LOG || fam == PLA_GLM_GAMMA_LOG; }
+constexpr bool glm_has_trials(int fam) { return fam == PLA_GLM_BINOMIAL_LOGIT || fam == PLA_GLM_BINOMIAL_PROBIT; }
+constexpr bool glm_has_obs_const(int fam) { return fam != PLA_GLM_LINPRED && fam != PLA_GLM_GAUSSIAN; }
 
 #ifndef PLA_GLM_SHARED_ONLY  // (pla_k_glm_terms.hip takes the shared parts; this kernel is pla_k_glm.hip's)
 __global__ __launch_bounds__(256) void glm_prepare_kernel(GlmPrepareParams P) {
@@ -116,8 +129,26 @@ __device__ __forceinline__ void glm_load_x(const double* xr, const double* zero,
   }
 }
 
+// logPhi(-|e|) and logPhi(|e|), Phi the standard normal distribution function, from one scaled complementary error function:
+// Phi(-|e|) = h exp(-w) with h = 0.5 erfcx(|e| / sqrt 2) and w = 0.5 e^2.  The lower tail is log(h) - w, finite and accurate where
+// log(0.5 erfc) underflows (below -38); the upper is log1p(-h exp(-w)).  erfcx varies slowly, so the rounding of |e| / sqrt 2 costs
+// an ulp.  The rounding of e^2 would enter exp(-w) as a relative error of w ulp -- erfc(|e| / sqrt 2) takes twice that from its
+// rounded argument -- and with y = trials the upper tail is all there is of ll: the square's remainder r = e^2 - fl(e^2), exact from
+// one fused multiply-add, is put back as the factor 1 - r / 2 (its own square is below 1e-26).
+__device__ __forceinline__ void glm_log_ndtr_pair(double eta, double* lower, double* upper) {
+#pragma clang fp contract(off)
+  const double h = 0.5 * erfcx(fabs(eta) * 0.70710678118654752440);
+  const double sq = eta * eta;
+  const double r = sq < HUGE_VAL ? fma(eta, eta, -sq) : 0.0;
+  const double w = 0.5 * sq;
+  *lower = log(h) - w;
+  *upper = log1p(-((h * exp(-w)) * (1.0 - 0.5 * r)));
+}
+
+// log_scale: log(sigma), PLA_GLM_NEGBINOMIAL_LOG alone
 template <int FAM>
-__device__ __forceinline__ double glm_density(double eta, double y, double trials, double obs_const, double sigma, double draw_const) {
+__device__ __forceinline__ double glm_density(double eta, double y, double trials, double obs_const, double sigma, double draw_const,
+                                              double log_scale = 0.0) {
 #pragma clang fp contract(off)
   if constexpr (FAM == PLA_GLM_GAUSSIAN) {
     const double t = (y - eta) / sigma;
@@ -127,9 +158,68 @@ __device__ __forceinline__ double glm_density(double eta, double y, double trial
     return (obs_const + y * eta) - trials * sp;
   } else if constexpr (FAM == PLA_GLM_POISSON_LOG) {
     return (obs_const + y * eta) - exp(eta);
+  } else if constexpr (FAM == PLA_GLM_NEGBINOMIAL_LOG) {
+    const double yp = y + sigma;
+    const double L = fmax(eta, log_scale) + log1p(exp(-fabs(eta - log_scale)));
+    return (((obs_const + draw_const) + lgamma(yp)) + y * eta) - yp * L;
+  } else if constexpr (FAM == PLA_GLM_GAMMA_LOG) {
+    return (draw_const + (sigma - 1.0) * obs_const) - sigma * (eta + y * exp(-eta));
+  } else if constexpr (FAM == PLA_GLM_BINOMIAL_PROBIT) {
+    double lower, upper;
+    glm_log_ndtr_pair(eta, &lower, &upper);
+    const bool neg = eta < 0.0;
+    const double m = trials - y;
+    const double a = y != 0.0 ? y * (neg ? lower : upper) : 0.0;
+    const double b = m != 0.0 ? m * (neg ? upper : lower) : 0.0;
+    return (obs_const + a) + b;
   } else {
     return eta;
   }
+}
+
+// The families whose density holds a special function (lgamma; erfc and erfcx) take the lane's four rows one after the other, in a
+// loop that is not unrolled: four inlined copies of such a function hold more polynomial coefficients in scalar registers than the
+// file has (they spill into vector lanes, and under the terms kernel's register cap into scratch) and quadruple the code.  The
+// loop works on entry 0 of the rows' values and rotates them by one entry per turn -- moves between registers, no indexed register
+// and no lane mask per entry; after the four turns every array stands as it stood.
+constexpr bool glm_rolled(int fam) { return fam == PLA_GLM_NEGBINOMIAL_LOG || fam == PLA_GLM_BINOMIAL_PROBIT; }
+
+__device__ __forceinline__ void glm_rotate(double (&v)[4]) {
+  const double first = v[0];
+  v[0] = v[1];
+  v[1] = v[2];
+  v[2] = v[3];
+  v[3] = first;
+}
+
+// the density of the lane's four rows, the NaN rule and the stores of a tile; returns the NaN entries replaced
+template <int FAM>
+__device__ __forceinline__ unsigned glm_rolled_epilogue(const GlmParams& P, double (&eta)[4], double (&yv)[4], double (&tv)[4], double (&cv)[4],
+                                                        double sig, double dc, double lsc, int64_t r0, int q, int s, bool s_ok) {
+  unsigned n_nan = 0;
+  // (the lane's address, its step and its rows left in vector registers: the loop holds no scalar of the launch but the counter's flag)
+  double* at = P.out + ((r0 + q) * P.pitch + s);
+  int64_t step = 4 * P.pitch, left = s_ok ? P.n_rows - (r0 + q) : 0;
+  asm volatile("" : "+v"(step), "+v"(left));
+  const bool count = P.replaced != nullptr;
+#pragma unroll 1
+  for (int g = 0; g < 4; ++g) {
+    double ll = glm_density<FAM>(eta[0], yv[0], tv[0], cv[0], sig, dc, lsc);
+    glm_rotate(eta);
+    glm_rotate(yv);
+    if constexpr (glm_has_trials(FAM)) glm_rotate(tv);
+    glm_rotate(cv);
+    if (left > 0) {
+      if (count && ll != ll) {
+        ll = -1e10;
+        n_nan += 1;
+      }
+      *at = ll;
+    }
+    at += step;
+    left -= 4;
+  }
+  return n_nan;
 }
 
 template <int FAM, int NCH, bool PANEL>
@@ -157,8 +247,8 @@ __global__ __launch_bounds__(kWave * kGlmWaves) void glm_kernel(GlmParams P) {
       const int64_t src = glm_source_row(P, r0 + q + 4 * g);
       ov[g] = P.offset ? P.offset[src] : 0.0;
       yv[g] = FAM != PLA_GLM_LINPRED ? P.y[src] : 0.0;
-      tv[g] = FAM == PLA_GLM_BINOMIAL_LOGIT && P.trials ? P.trials[src] : 1.0;
-      cv[g] = (FAM == PLA_GLM_BINOMIAL_LOGIT || FAM == PLA_GLM_POISSON_LOG) && P.obs_const ? P.obs_const[src] : 0.0;
+      tv[g] = glm_has_trials(FAM) && P.trials ? P.trials[src] : 1.0;
+      cv[g] = glm_has_obs_const(FAM) && P.obs_const ? P.obs_const[src] : 0.0;
     }
     const int t_end = (st + 1) * P.strip_tiles < n_dtiles ? (st + 1) * P.strip_tiles : n_dtiles;
 #pragma unroll 1
@@ -181,16 +271,24 @@ __global__ __launch_bounds__(kWave * kGlmWaves) void glm_kernel(GlmParams P) {
       }
       // ---- epilogue: C / D col = lane & 15 (the draw), row = (lane >> 4) + 4 reg
       const bool s_ok = s < S;
-      double sig = 1.0, dc = 0.0;
-      if constexpr (FAM == PLA_GLM_GAUSSIAN) {
+      double sig = 1.0, dc = 0.0, lsc = 0.0;
+      if constexpr (glm_draw_values(FAM)) {
         sig = P.sigma[s_ok ? s : S - 1];
         dc = P.draw_const[s_ok ? s : S - 1];
+      }
+      if constexpr (FAM == PLA_GLM_NEGBINOMIAL_LOG) lsc = log(sig);
+      if constexpr (glm_rolled(FAM)) {
+        double eta[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) eta[g] = acc[g] + ov[g];
+        n_nan += glm_rolled_epilogue<FAM>(P, eta, yv, tv, cv, sig, dc, lsc, r0, q, s, s_ok);
+        continue;
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
 #pragma clang fp contract(off)
         const double eta = acc[g] + ov[g];
-        double ll = glm_density<FAM>(eta, yv[g], tv[g], cv[g], sig, dc);
+        double ll = glm_density<FAM>(eta, yv[g], tv[g], cv[g], sig, dc, lsc);
         const int64_t r = r0 + q + 4 * g;
         if (s_ok && r < P.n_rows) {
           if (P.replaced && ll != ll) {
@@ -207,6 +305,18 @@ __global__ __launch_bounds__(kWave * kGlmWaves) void glm_kernel(GlmParams P) {
     for (int d = 32; d >= 1; d >>= 1) n_nan += __shfl_xor(n_nan, d);
     if (lane == 0 && n_nan) atomicAdd(P.replaced, n_nan);
   }
+}
+
+// the instantiation of a family for the padded predictor count of a launch
+template <int FAM>
+inline hipError_t glm_launch_family(const GlmParams& p, unsigned grid, hipStream_t stream) {
+  const dim3 block(kWave * kGlmWaves);
+  if (p.p_pad > kGlmK * kGlmPanel) hipLaunchKernelGGL((glm_kernel<FAM, kGlmPanel, true>), dim3(grid), block, 0, stream, p);
+  else if (p.p_pad == kGlmK * 8) hipLaunchKernelGGL((glm_kernel<FAM, 8, false>), dim3(grid), block, 0, stream, p);
+  else if (p.p_pad == kGlmK * 4) hipLaunchKernelGGL((glm_kernel<FAM, 4, false>), dim3(grid), block, 0, stream, p);
+  else if (p.p_pad == kGlmK * 2) hipLaunchKernelGGL((glm_kernel<FAM, 2, false>), dim3(grid), block, 0, stream, p);
+  else hipLaunchKernelGGL((glm_kernel<FAM, 1, false>), dim3(grid), block, 0, stream, p);
+  return hipGetLastError();
 }
 
 }  // namespace pla

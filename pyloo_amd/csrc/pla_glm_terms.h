@@ -46,6 +46,10 @@ struct GlmTermsParams {
 
 constexpr int kGlmTermsTile = 8;  // groups / draws per wavefront tile of the prepare pass
 
+// the families pla_k_glm_terms.hip does not instantiate (pla_k_glm_terms_families.hip); *name: the family as the route text names it
+hipError_t launch_glm_terms_more(int family, const GlmTermsParams& p, unsigned grid, hipStream_t stream, const char** name);
+
+#ifndef PLA_GLM_TERMS_SHARED_ONLY  // (pla_k_glm_terms_families.hip takes the shared parts; this kernel is pla_k_glm_terms.hip's)
 __global__ __launch_bounds__(256) void glm_terms_prepare_kernel(GlmTermsPrepareParams P) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t total = P.first[kGlmMaxTerms];
@@ -65,10 +69,12 @@ __global__ __launch_bounds__(256) void glm_terms_prepare_kernel(GlmTermsPrepareP
     P.uimg[row * (int64_t)P.s_pad + s] = v;
   }
 }
+#endif
 
-// (one or two chunks in registers: held to the 128 registers of four wavefronts per SIMD, which the epilogue's `exp` / `log1p` want)
+// (one or two chunks in registers: held to the 128 registers of four wavefronts per SIMD, which the epilogue's `exp` / `log1p` want;
+// not the families of glm_rolled: lgamma, erfc and erfcx under that cap go to scratch)
 template <int FAM, int NCH, bool PANEL>
-__global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_eu(NCH <= 2 ? 4 : 1))) void glm_terms_kernel(GlmTermsParams T) {
+__global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_eu(NCH <= 2 && !glm_rolled(FAM) ? 4 : 1))) void glm_terms_kernel(GlmTermsParams T) {
   const GlmParams& P = T.glm;
   const int S = P.n_draws;
   const int lane = threadIdx.x & (kWave - 1), i = lane & 15, q = lane >> 4;
@@ -77,7 +83,8 @@ __global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_
   const int n_panels = PANEL ? P.p_pad / (kGlmK * NCH) : 1;
   const int64_t n_units = (P.n_rows + kGlmTile - 1) / kGlmTile * P.n_strips;
   const int64_t nw = (int64_t)gridDim.x * kGlmWaves;
-  const int64_t img_pitch = P.s_pad;
+  int64_t img_pitch = P.s_pad;
+  if constexpr (glm_rolled(FAM)) asm volatile("" : "+v"(img_pitch));  // (a lane's multiplier: these kernels have no scalar register to spare)
   unsigned long long n_nan = 0;
   for (int64_t u = (int64_t)blockIdx.x * kGlmWaves + wv; u < n_units; u += nw) {
     const int64_t rt = u / P.n_strips;
@@ -95,8 +102,8 @@ __global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_
       src[g] = glm_source_row(P, r0 + q + 4 * g);
       ov[g] = P.offset ? P.offset[src[g]] : 0.0;
       yv[g] = FAM != PLA_GLM_LINPRED ? P.y[src[g]] : 0.0;
-      tv[g] = FAM == PLA_GLM_BINOMIAL_LOGIT && P.trials ? P.trials[src[g]] : 1.0;
-      cv[g] = (FAM == PLA_GLM_BINOMIAL_LOGIT || FAM == PLA_GLM_POISSON_LOG) && P.obs_const ? P.obs_const[src[g]] : 0.0;
+      tv[g] = glm_has_trials(FAM) && P.trials ? P.trials[src[g]] : 1.0;
+      cv[g] = glm_has_obs_const(FAM) && P.obs_const ? P.obs_const[src[g]] : 0.0;
     }
     const int t_end = (st + 1) * P.strip_tiles < n_dtiles ? (st + 1) * P.strip_tiles : n_dtiles;
 #pragma unroll 1
@@ -119,11 +126,12 @@ __global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_
       }
       // ---- epilogue: C / D col = lane & 15 (the draw), row = (lane >> 4) + 4 reg
       const bool s_ok = s < S;
-      double sig = 1.0, dc = 0.0;
-      if constexpr (FAM == PLA_GLM_GAUSSIAN) {
+      double sig = 1.0, dc = 0.0, lsc = 0.0;
+      if constexpr (glm_draw_values(FAM)) {
         sig = P.sigma[s_ok ? s : S - 1];
         dc = P.draw_const[s_ok ? s : S - 1];
       }
+      if constexpr (FAM == PLA_GLM_NEGBINOMIAL_LOG) lsc = log(sig);
       double eta[4];
       {
 #pragma clang fp contract(off)
@@ -163,9 +171,13 @@ __global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_
           }
         }
       }
+      if constexpr (glm_rolled(FAM)) {
+        n_nan += glm_rolled_epilogue<FAM>(P, eta, yv, tv, cv, sig, dc, lsc, r0, q, s, s_ok);
+        continue;
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        double ll = glm_density<FAM>(eta[g], yv[g], tv[g], cv[g], sig, dc);
+        double ll = glm_density<FAM>(eta[g], yv[g], tv[g], cv[g], sig, dc, lsc);
         const int64_t r = r0 + q + 4 * g;
         if (s_ok && r < P.n_rows) {
           if (P.replaced && ll != ll) {
@@ -182,6 +194,19 @@ __global__ __launch_bounds__(kWave * kGlmWaves) __attribute__((amdgpu_waves_per_
     for (int d = 32; d >= 1; d >>= 1) n_nan += __shfl_xor(n_nan, d);
     if (lane == 0 && n_nan) atomicAdd(P.replaced, n_nan);
   }
+}
+
+// the instantiation of a family for the padded predictor count of a launch
+template <int FAM>
+inline hipError_t glm_terms_launch_family(const GlmTermsParams& p, unsigned grid, hipStream_t stream) {
+  const dim3 block(kWave * kGlmWaves);
+  const int p_pad = p.glm.p_pad;
+  if (p_pad > kGlmK * kGlmPanel) hipLaunchKernelGGL((glm_terms_kernel<FAM, kGlmPanel, true>), dim3(grid), block, 0, stream, p);
+  else if (p_pad == kGlmK * 8) hipLaunchKernelGGL((glm_terms_kernel<FAM, 8, false>), dim3(grid), block, 0, stream, p);
+  else if (p_pad == kGlmK * 4) hipLaunchKernelGGL((glm_terms_kernel<FAM, 4, false>), dim3(grid), block, 0, stream, p);
+  else if (p_pad == kGlmK * 2) hipLaunchKernelGGL((glm_terms_kernel<FAM, 2, false>), dim3(grid), block, 0, stream, p);
+  else hipLaunchKernelGGL((glm_terms_kernel<FAM, 1, false>), dim3(grid), block, 0, stream, p);
+  return hipGetLastError();
 }
 
 }  // namespace pla

@@ -37,17 +37,6 @@ hipError_t launch_glm_prepare(const double* beta, int64_t stride_draw, int64_t s
   return hipSuccess;
 }
 
-template <int FAM>
-static hipError_t launch_glm_family(const GlmParams& p, unsigned grid, hipStream_t stream) {
-  constexpr int block = kWave * kGlmWaves;
-  if (p.p_pad > kGlmK * kGlmPanel) PLA_GLM_LAUNCH((glm_kernel<FAM, kGlmPanel, true>), grid, block);
-  else if (p.p_pad == kGlmK * 8) PLA_GLM_LAUNCH((glm_kernel<FAM, 8, false>), grid, block);
-  else if (p.p_pad == kGlmK * 4) PLA_GLM_LAUNCH((glm_kernel<FAM, 4, false>), grid, block);
-  else if (p.p_pad == kGlmK * 2) PLA_GLM_LAUNCH((glm_kernel<FAM, 2, false>), grid, block);
-  else PLA_GLM_LAUNCH((glm_kernel<FAM, 1, false>), grid, block);
-  return hipSuccess;
-}
-
 unsigned glm_fill_params(const GlmLaunch& g, GlmParams* out) {
   GlmParams& p = *out;
   p = GlmParams{};
@@ -90,14 +79,15 @@ hipError_t launch_glm(const GlmLaunch& g, hipStream_t stream, char* route, int c
   GlmParams p;
   const unsigned grid = glm_fill_params(g, &p);
   hipError_t e;
-  const char* name;
+  const char* name = "";
   switch (g.family) {
-    case PLA_GLM_GAUSSIAN: e = launch_glm_family<PLA_GLM_GAUSSIAN>(p, grid, stream); name = "gaussian"; break;
-    case PLA_GLM_BINOMIAL_LOGIT: e = launch_glm_family<PLA_GLM_BINOMIAL_LOGIT>(p, grid, stream); name = "binomial logit"; break;
-    case PLA_GLM_POISSON_LOG: e = launch_glm_family<PLA_GLM_POISSON_LOG>(p, grid, stream); name = "poisson log"; break;
-    case PLA_GLM_LINPRED: e = launch_glm_family<PLA_GLM_LINPRED>(p, grid, stream); name = "linear predictor"; break;
-    default: return hipErrorInvalidValue;
+    case PLA_GLM_GAUSSIAN: e = glm_launch_family<PLA_GLM_GAUSSIAN>(p, grid, stream); name = "gaussian"; break;
+    case PLA_GLM_BINOMIAL_LOGIT: e = glm_launch_family<PLA_GLM_BINOMIAL_LOGIT>(p, grid, stream); name = "binomial logit"; break;
+    case PLA_GLM_POISSON_LOG: e = glm_launch_family<PLA_GLM_POISSON_LOG>(p, grid, stream); name = "poisson log"; break;
+    case PLA_GLM_LINPRED: e = glm_launch_family<PLA_GLM_LINPRED>(p, grid, stream); name = "linear predictor"; break;
+    default: e = launch_glm_more(g.family, p, grid, stream, &name);  // (pla_k_glm_families.hip)
   }
+  if (e == hipErrorInvalidValue) return e;  // (a family nobody has)
   if (route) {
     const int nch = p.p_pad > kGlmK * kGlmPanel ? kGlmPanel : p.p_pad / kGlmK;
     snprintf(route, cap, "glm_kernel<%s, %d chunks of 16 predictors%s>", name, nch, p.p_pad > kGlmK * kGlmPanel ? " per panel" : " in registers");

@@ -50,18 +50,6 @@ hipError_t launch_glm_terms_prepare(GlmTerms* t, int n_draws, double* uimg, hipS
   return hipSuccess;
 }
 
-template <int FAM>
-static hipError_t launch_glm_terms_family(const GlmTermsParams& p, unsigned grid, hipStream_t stream) {
-  constexpr int block = kWave * kGlmWaves;
-  const int p_pad = p.glm.p_pad;
-  if (p_pad > kGlmK * kGlmPanel) PLA_GLM_TERMS_LAUNCH((glm_terms_kernel<FAM, kGlmPanel, true>), grid, block);
-  else if (p_pad == kGlmK * 8) PLA_GLM_TERMS_LAUNCH((glm_terms_kernel<FAM, 8, false>), grid, block);
-  else if (p_pad == kGlmK * 4) PLA_GLM_TERMS_LAUNCH((glm_terms_kernel<FAM, 4, false>), grid, block);
-  else if (p_pad == kGlmK * 2) PLA_GLM_TERMS_LAUNCH((glm_terms_kernel<FAM, 2, false>), grid, block);
-  else PLA_GLM_TERMS_LAUNCH((glm_terms_kernel<FAM, 1, false>), grid, block);
-  return hipSuccess;
-}
-
 hipError_t launch_glm_terms(const GlmLaunch& g, const GlmTerms& t, hipStream_t stream, char* route, int cap) {
   if (t.n_terms == 0) return launch_glm(g, stream, route, cap);  // (no terms: the kernel of pla_glm.h itself)
   if (route && cap > 0) route[0] = 0;
@@ -79,14 +67,15 @@ hipError_t launch_glm_terms(const GlmLaunch& g, const GlmTerms& t, hipStream_t s
     p.last_group[k] = t.n_groups[k] - 1;
   }
   hipError_t e;
-  const char* name;
+  const char* name = "";
   switch (g.family) {
-    case PLA_GLM_GAUSSIAN: e = launch_glm_terms_family<PLA_GLM_GAUSSIAN>(p, grid, stream); name = "gaussian"; break;
-    case PLA_GLM_BINOMIAL_LOGIT: e = launch_glm_terms_family<PLA_GLM_BINOMIAL_LOGIT>(p, grid, stream); name = "binomial logit"; break;
-    case PLA_GLM_POISSON_LOG: e = launch_glm_terms_family<PLA_GLM_POISSON_LOG>(p, grid, stream); name = "poisson log"; break;
-    case PLA_GLM_LINPRED: e = launch_glm_terms_family<PLA_GLM_LINPRED>(p, grid, stream); name = "linear predictor"; break;
-    default: return hipErrorInvalidValue;
+    case PLA_GLM_GAUSSIAN: e = glm_terms_launch_family<PLA_GLM_GAUSSIAN>(p, grid, stream); name = "gaussian"; break;
+    case PLA_GLM_BINOMIAL_LOGIT: e = glm_terms_launch_family<PLA_GLM_BINOMIAL_LOGIT>(p, grid, stream); name = "binomial logit"; break;
+    case PLA_GLM_POISSON_LOG: e = glm_terms_launch_family<PLA_GLM_POISSON_LOG>(p, grid, stream); name = "poisson log"; break;
+    case PLA_GLM_LINPRED: e = glm_terms_launch_family<PLA_GLM_LINPRED>(p, grid, stream); name = "linear predictor"; break;
+    default: e = launch_glm_terms_more(g.family, p, grid, stream, &name);  // (pla_k_glm_terms_families.hip)
   }
+  if (e == hipErrorInvalidValue) return e;  // (a family nobody has)
   if (route) {
     const bool panel = p.glm.p_pad > kGlmK * kGlmPanel;
     snprintf(route, cap, "glm_terms_kernel<%s, %d chunks of 16 predictors%s, %d group-level terms>", name, panel ? kGlmPanel : p.glm.p_pad / kGlmK,

@@ -250,7 +250,7 @@ struct GlmLaunch {
   int64_t r_first, n_rows;
   const double* bimg;
   int n_pred, n_draws;
-  const double *y, *offset, *trials, *obs_const, *sigma, *draw_const;
+  const double *y, *offset, *trials, *obs_const, *sigma, *draw_const;  // sigma: the family's scale per draw (sigma, phi, alpha)
   double* out;
   int64_t pitch;
   unsigned long long* replaced;

@@ -1,6 +1,6 @@
 // Host-side pieces shared by the translation units of libpyloo_amd.so (internal).  The kernels are compiled as several
 // units in parallel (pyloo_amd/build.py): pla_k_general.hip (general kernel, reductions, dispatcher), pla_k_wave_f64/f32.hip,
-// pla_k_chunked_f64/f32.hip, pla_k_fit.hip, pla_k_waic.hip, pla_k_col.hip, pla_k_eloo.hip, pla_k_group.hip, pla_k_compare.hip, pla_k_nonfactor.hip, pla_k_draws.hip, pla_k_kfold.hip, pla_k_mm.hip, pla_k_mixis.hip, pla_k_pit.hip, pla_k_lfo.hip, pla_k_lfo_bw.hip, pla_k_ess.hip, pla_k_diag.hip, pla_k_influence.hip, pla_k_glm.hip; each launches the kernels it defines.  The C ABI behind them is split the same way: pla_capi.h and the units pla_capi_<family>.hip.
+// pla_k_chunked_f64/f32.hip, pla_k_fit.hip, pla_k_waic.hip, pla_k_col.hip, pla_k_eloo.hip, pla_k_group.hip, pla_k_compare.hip, pla_k_nonfactor.hip, pla_k_draws.hip, pla_k_kfold.hip, pla_k_mm.hip, pla_k_mixis.hip, pla_k_pit.hip, pla_k_lfo.hip, pla_k_lfo_bw.hip, pla_k_ess.hip, pla_k_diag.hip, pla_k_influence.hip, pla_k_glm.hip, pla_k_glm_terms.hip, pla_k_glm_marginal.hip, pla_k_glm_families.hip, pla_k_glm_terms_families.hip; each launches the kernels it defines.  The C ABI behind them is split the same way: pla_capi.h and the units pla_capi_<family>.hip.
 #pragma once
 
 #include <cstdlib>

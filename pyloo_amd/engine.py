@@ -895,7 +895,8 @@ class Engine:
             mode="matrix", tail_count=0, method="psis", scale_value=1.0, good_k=0.7, pointwise=True, aggregate=True, groups=None):
         """The log-likelihood of a generalised linear model from its design matrix ``X`` (n_obs, P), the coefficient draws ``beta``
         (n_draws, P) and the family (``pla_glm``): ``"linpred"`` (eta itself), ``"gaussian"``, ``"binomial"`` (logit link), ``"poisson"``
-        (log link).  ``y``, ``offset``, ``trials``, ``obs_const`` are [n_obs], ``draw_scale`` and ``draw_const`` [n_draws] (Gaussian);
+        (log link), ``"negbinomial"`` (log link), ``"gamma"`` (log link), ``"binomial_probit"``.  ``y``, ``offset``, ``trials``,
+        ``obs_const`` are [n_obs], ``draw_scale`` and ``draw_const`` [n_draws] (Gaussian sigma, negative-binomial phi, gamma shape);
         the constants are the caller's (include/pyloo_amd.h).  ``rows``: optional observation indices, one output row per index.
         ``mode="matrix"`` returns the (m, n_draws) matrix; ``mode="loo"`` consumes it block by block in the PSIS-LOO pass and returns
         ``dict(diag, loo_i, lppd_i, agg, n_replaced)``.  NumPy ``X`` -> NumPy out; CUDA tensor -> CUDA tensors, everything else is
@@ -919,7 +920,8 @@ class Engine:
         """The argument block of ``pla_glm`` without its outputs, in the memory space of ``X`` -> ``(space, block, terms, what to keep
         alive over the call, rows of the call, n_draws)``; ``terms``: one tuple of ``pla_glm_term`` entries per term of ``groups``."""
         fam = {"linpred": _capi.PLA_GLM_LINPRED, "gaussian": _capi.PLA_GLM_GAUSSIAN, "binomial": _capi.PLA_GLM_BINOMIAL_LOGIT,
-               "poisson": _capi.PLA_GLM_POISSON_LOG}
+               "poisson": _capi.PLA_GLM_POISSON_LOG, "negbinomial": _capi.PLA_GLM_NEGBINOMIAL_LOG, "gamma": _capi.PLA_GLM_GAMMA_LOG,
+               "binomial_probit": _capi.PLA_GLM_BINOMIAL_PROBIT}
         if family not in fam:
             raise ValueError(f"family must be one of {sorted(fam)}, got {family!r}")
         if mode not in ("matrix", "loo"):
@@ -1010,8 +1012,8 @@ class Engine:
         ``nodes`` / ``log_weights`` (C, n_nodes).  ``tau`` is [n_draws], ``z`` [n_obs] or None (1); everything else is :meth:`glm`'s,
         ``family="linpred"`` and ``rows`` excepted.  ``mode="matrix"`` returns the (C, n_draws) matrix, ``mode="loo"`` the dict of
         the fused PSIS-LOO pass with one entry per cluster.  A CUDA ``X`` waits once for the offsets of ``index``."""
-        if family == "linpred":
-            raise ValueError("glm_marginal needs a likelihood: family must be 'gaussian', 'binomial' or 'poisson'")
+        if family not in ("gaussian", "binomial", "poisson"):
+            raise ValueError(f"glm_marginal needs a likelihood: family must be 'gaussian', 'binomial' or 'poisson', got {family!r}")
         sp, args, terms, keep, n, s = self._glm_block(X, beta, family, y, offset, trials, obs_const, draw_scale, draw_const, None, mode,
                                                       tail_count, method, scale_value, good_k, groups)
         n_clusters = int(index.n_groups)

@@ -10,8 +10,10 @@ the unchanged PSIS-LOO pass consumes each block before the next overwrites it.
 * ``loo_glm``                the same with ``beta`` taken from the ``posterior`` group of ``idata``
 * ``loo_subsample_glm``      subsampled LOO at an N for which no matrix can exist
 
-Families: ``"gaussian"`` (identity link, ``sigma`` per draw), ``"bernoulli"`` and ``"binomial"`` (logit link), ``"poisson"`` (log
-link).  NumPy ``X`` -> NumPy results; a torch CUDA ``X`` -> everything is moved to its device and stays there.  The fronts compute
+Families: ``"gaussian"`` (identity link, ``sigma`` per draw), ``"bernoulli"`` and ``"binomial"`` (logit link, or
+``link="probit"``), ``"poisson"`` (log link), ``"negbinomial"`` (log link, ``phi`` per draw: NB2 with mean ``mu = exp(eta)`` and
+variance ``mu + mu^2 / phi``) and ``"gamma"`` (log link, ``shape`` per draw: mean ``exp(eta)``, rate ``shape / mean``).  ``link=None``
+is the canonical link named above.  NumPy ``X`` -> NumPy results; a torch CUDA ``X`` -> everything is moved to its device and stays there.  The fronts compute
 the per-observation and per-draw constants the kernel is handed (``obs_const``, ``draw_const``): ``scipy.special.gammaln`` /
 ``np.log`` on the host, ``torch.lgamma`` / ``torch.log`` on the device.
 
@@ -35,10 +37,13 @@ from .utils import to_inference_data
 
 __all__ = ["glm_log_lik", "glm_plpd", "loo_glm_from_design", "loo_glm", "loo_subsample_glm"]
 
-FAMILIES = ("gaussian", "bernoulli", "binomial", "poisson")
+FAMILIES = ("gaussian", "bernoulli", "binomial", "poisson", "negbinomial", "gamma")
 MAX_PREDICTORS = 256
 MAX_TERMS = 8
-_ENGINE_FAMILY = {"gaussian": "gaussian", "bernoulli": "binomial", "binomial": "binomial", "poisson": "poisson"}
+_ENGINE_FAMILY = {"gaussian": "gaussian", "bernoulli": "binomial", "binomial": "binomial", "poisson": "poisson",
+                  "negbinomial": "negbinomial", "gamma": "gamma"}
+_CANONICAL_LINK = {"gaussian": "identity", "bernoulli": "logit", "binomial": "logit", "poisson": "log", "negbinomial": "log", "gamma": "log"}
+_SCALE_ARGUMENT = {"gaussian": "sigma", "negbinomial": "phi", "gamma": "shape"}  # what travels as the engine's draw_scale
 _HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
 
 
@@ -46,11 +51,40 @@ def _all(flag):
     return bool(flag.all().item()) if hasattr(flag, "item") else bool(np.all(flag))
 
 
-def _prepare(X, y, beta, family, sigma, offset, trials):
+def _engine_family(family, link=None):
+    """The engine's name of a family of FAMILIES under ``link``: None and the canonical link are one path, ``"probit"`` goes on the
+    two binomial families."""
+    probit_too = family in ("bernoulli", "binomial")
+    if link is None or link == _CANONICAL_LINK[family]:
+        return _ENGINE_FAMILY[family]
+    if link == "probit" and probit_too:
+        return "binomial_probit"
+    takes = f"None, {_CANONICAL_LINK[family]!r}" + (" or 'probit'" if probit_too else "")
+    raise ValueError(f"link of the {family} family must be {takes}, got {link!r}")
+
+
+def _draw_const(family, scale):
+    """The per-draw constant of a family with a scale per draw, NumPy or torch: ``-0.5 log(2 pi) - log(sigma)`` for the Gaussian,
+    ``a log(a) - lgamma(a)`` for ``a`` = ``phi`` of the negative binomial or the gamma family's ``shape``."""
+    if _is_torch_tensor(scale):
+        import torch
+
+        lgamma, log = torch.lgamma, torch.log
+    else:
+        from scipy.special import gammaln as lgamma
+
+        log = np.log
+    if family == "gaussian":
+        return -_HALF_LOG_2PI - log(scale)
+    return scale * log(scale) - lgamma(scale)
+
+
+def _prepare(X, y, beta, family, sigma, offset, trials, phi=None, shape=None, link=None):
     """Every check of the fronts, before any engine call, and the vectors the engine is handed -- in the memory space of ``X``.
     Returns ``(X, beta, dict(y, offset, trials, obs_const, draw_scale, draw_const))``."""
     if family not in FAMILIES:
         raise ValueError(f"family must be one of {', '.join(FAMILIES)}, got {family!r}")
+    _engine_family(family, link)
     tensor = _is_torch_tensor(X)
     if tensor:
         import torch
@@ -94,6 +128,19 @@ def _prepare(X, y, beta, family, sigma, offset, trials):
             raise ValueError("sigma must be finite and positive")
     elif sigma is not None:
         raise ValueError(f"sigma belongs to the gaussian family, not to {family!r}")
+    for name, owner, value in (("phi", "negbinomial", phi), ("shape", "gamma", shape)):
+        if family != owner:
+            if value is not None:
+                raise ValueError(f"{name} belongs to the {owner} family, not to {family!r}")
+            continue
+        if value is None:
+            raise ValueError(f"the {owner} family needs {name}, one value per draw")
+        value = vec(value).reshape(-1)
+        if value.shape[0] != s:
+            raise ValueError(f"{name} needs {s} values, one per draw, got {value.shape[0]}")
+        if not _all(finite(value) & (value > 0)):
+            raise ValueError(f"{name} must be finite and positive")
+        sigma = value  # (the engine's draw_scale)
     if family == "binomial":
         if trials is None:
             raise ValueError("the binomial family needs trials (family='bernoulli' is one trial each)")
@@ -104,7 +151,10 @@ def _prepare(X, y, beta, family, sigma, offset, trials):
             raise ValueError("trials must be non-negative integers")
     elif trials is not None:
         raise ValueError(f"trials belongs to the binomial family, not to {family!r}")
-    if family != "gaussian":
+    if family == "gamma":
+        if not _all(finite(y) & (y > 0)):
+            raise ValueError("y of the gamma family must be finite and positive")
+    elif family != "gaussian":
         if not _all(finite(y) & (y >= 0) & (floor(y) == y)):
             raise ValueError(f"y of the {family} family must be non-negative integers")
         if family == "bernoulli" and not _all(y <= 1):
@@ -117,10 +167,12 @@ def _prepare(X, y, beta, family, sigma, offset, trials):
     obs_const = draw_const = None
     if family == "binomial":
         obs_const = (lgamma(trials + 1.0) - lgamma(y + 1.0)) - lgamma(trials - y + 1.0)
-    elif family == "poisson":
+    elif family in ("poisson", "negbinomial"):
         obs_const = -lgamma(y + 1.0)
-    elif family == "gaussian":
-        draw_const = -_HALF_LOG_2PI - log(sigma)
+    elif family == "gamma":
+        obs_const = log(y)
+    if family in _SCALE_ARGUMENT:
+        draw_const = _draw_const(family, sigma)
     return X, beta, {"y": y, "offset": offset, "trials": trials, "obs_const": obs_const, "draw_scale": sigma, "draw_const": draw_const}
 
 
@@ -198,26 +250,29 @@ def _check_reff(reff):
     return float(reff)
 
 
-def glm_log_lik(X, y, beta, family, sigma=None, offset=None, trials=None, rows=None, linpred=False, groups=None):
+def glm_log_lik(X, y, beta, family, sigma=None, offset=None, trials=None, rows=None, linpred=False, groups=None, *, phi=None,
+                shape=None, link=None):
     """The ``(m, S)`` log-likelihood matrix of a GLM -- of all N rows of ``X``, or of ``rows`` (any order, repeats allowed) -- or,
     with ``linpred=True``, the posterior linear predictor ``X @ beta.T + offset`` (plus the terms of ``groups``, see the module's
-    text).  torch on the device for a CUDA ``X``, NumPy otherwise."""
-    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    text).  ``phi`` [S]: the dispersion of ``family="negbinomial"``; ``shape`` [S]: the shape of ``family="gamma"``; ``link``: None
+    (canonical) or ``"probit"`` on the binomial families.  torch on the device for a CUDA ``X``, NumPy otherwise."""
+    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials, phi, shape, link)
     terms = _prepare_groups(groups, Xc, bc.shape[0])
     eng = _engine_of(Xc)
     if linpred:
         return eng.glm(Xc, bc, "linpred", offset=v["offset"], rows=rows, **_with_groups(terms))
-    return eng.glm(Xc, bc, _ENGINE_FAMILY[family], rows=rows, **v, **_with_groups(terms))
+    return eng.glm(Xc, bc, _engine_family(family, link), rows=rows, **v, **_with_groups(terms))
 
 
-def _posterior_mean(beta, v):
-    """``beta`` and the per-draw vectors of ``v`` at the posterior mean: one draw."""
+def _posterior_mean(beta, v, family="gaussian"):
+    """``beta`` and the per-draw vectors of ``v`` at the posterior mean: one draw.  The constant of the draw is evaluated again at
+    the mean of ``sigma`` / ``phi`` / ``shape``."""
     b1 = beta.mean(0).reshape(1, -1)
     v1 = dict(v)
     if v["draw_scale"] is not None:
         s1 = v["draw_scale"].mean().reshape(1)
         v1["draw_scale"] = s1
-        v1["draw_const"] = -_HALF_LOG_2PI - (s1.log() if hasattr(s1, "log") else np.log(s1))
+        v1["draw_const"] = _draw_const(family, s1)
     return b1, v1
 
 
@@ -225,25 +280,27 @@ def _mean_draw(draws):
     return draws.mean(0).reshape(1, -1)
 
 
-def glm_plpd(X, y, beta, family, sigma=None, offset=None, trials=None, groups=None):
-    """``[N]``: the log-likelihood of every observation at the posterior mean of ``beta`` (of ``sigma``, and of the draws of every
-    term of ``groups``) -- the point log predictive density of Magnusson et al. (2019), the matrix mode with one draw."""
-    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+def glm_plpd(X, y, beta, family, sigma=None, offset=None, trials=None, groups=None, *, phi=None, shape=None, link=None):
+    """``[N]``: the log-likelihood of every observation at the posterior mean of ``beta`` (of ``sigma`` / ``phi`` / ``shape``, and of
+    the draws of every term of ``groups``) -- the point log predictive density of Magnusson et al. (2019), the matrix mode with one
+    draw."""
+    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials, phi, shape, link)
     terms = _prepare_groups(groups, Xc, bc.shape[0])
-    b1, v1 = _posterior_mean(bc, v)
-    return _engine_of(Xc).glm(Xc, b1, _ENGINE_FAMILY[family], **v1, **_with_groups(_groups_at(terms, _mean_draw))).reshape(-1)
+    b1, v1 = _posterior_mean(bc, v, family)
+    return _engine_of(Xc).glm(Xc, b1, _engine_family(family, link), **v1, **_with_groups(_groups_at(terms, _mean_draw))).reshape(-1)
 
 
 def loo_glm_from_design(X, y, beta, family, sigma=None, offset=None, trials=None, reff=1.0, scale=None, method="psis", pointwise=False,
-                        rows=None, groups=None):
+                        rows=None, groups=None, *, phi=None, shape=None, link=None):
     """PSIS-LOO of a GLM from its design matrix ``X`` (N, P), the outcomes ``y`` [N] and the draws ``beta`` (S, P), in one fused
     pass: per block of observations the log-likelihood is generated into a bounded buffer and consumed by the LOO kernels.
     Returns the ``ELPDData`` of ``loo_from_matrix`` on the materialised matrix -- the same keys, warnings and texts.  ``rows``:
-    the pass over these observations only.  ``groups``: the group-level terms of a multilevel model (the module's text)."""
+    the pass over these observations only.  ``groups``: the group-level terms of a multilevel model (the module's text).  ``phi``,
+    ``shape``, ``link``: as ``glm_log_lik`` takes them."""
     method = parse_method(method)
     scale, scale_value = _scale_value(scale)
     reff = _check_reff(reff)
-    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials, phi, shape, link)
     terms = _prepare_groups(groups, Xc, bc.shape[0])
     n_samples = bc.shape[0]
     if n_samples < 2:
@@ -252,7 +309,7 @@ def loo_glm_from_design(X, y, beta, family, sigma=None, offset=None, trials=None
     M = tail_count_for(n_samples, reff) if method == ISMethod.PSIS else 0
     if method == ISMethod.PSIS and M + 1 > n_samples:
         raise IndexError(f"index {-M - 1} is out of bounds for axis 0 with size {n_samples}")
-    res = _engine_of(Xc).glm(Xc, bc, _ENGINE_FAMILY[family], rows=rows, mode="loo", tail_count=M, method=method.value,
+    res = _engine_of(Xc).glm(Xc, bc, _engine_family(family, link), rows=rows, mode="loo", tail_count=M, method=method.value,
                              scale_value=scale_value, good_k=good_k, **v, **_with_groups(terms))
     if int(res["n_replaced"]) > 0:
         warnings.warn("NaN values detected in log-likelihood. These will be ignored in the LOO calculation.", UserWarning, stacklevel=2)
@@ -266,22 +323,25 @@ def loo_glm_from_design(X, y, beta, family, sigma=None, offset=None, trials=None
 
 
 def loo_glm(idata, X, y, family, var_names, sigma_name=None, var_name=None, offset=None, trials=None, reff=1.0, scale=None,
-            method="psis", pointwise=False, rows=None, group_terms=None):
+            method="psis", pointwise=False, rows=None, group_terms=None, *, phi_name=None, shape_name=None, link=None):
     """``loo_glm_from_design`` with the draws taken from ``idata``: the columns of ``beta`` are the variables ``var_names`` of the
     ``posterior`` group, each flattened over its own dimensions, in the order given; their count must equal ``X.shape[1]``.
-    ``sigma_name``: the posterior variable that holds the Gaussian scale.  ``y=None`` reads ``observed_data[var_name]``.
+    ``sigma_name``: the posterior variable that holds the Gaussian scale; ``phi_name`` / ``shape_name``: the one that holds the
+    dispersion of the negative binomial / the shape of the gamma family; ``link``: as ``glm_log_lik`` takes it.  ``y=None`` reads ``observed_data[var_name]``.
     ``group_terms``: a sequence of ``(name, index)`` or ``(name, index, z)`` -- the posterior variable ``name`` of shape
     ``(chain, draw, G)`` holds the group effects of the term --, handed on as ``groups`` in the order given."""
     data = to_inference_data(idata)
     beta, names, _ = _posterior_columns(data, var_names)
     if beta.shape[1] != X.shape[1]:
         raise ValueError(f"var_names give {beta.shape[1]} columns ({', '.join(names)}) for the {X.shape[1]} columns of X")
-    sigma = None
-    if sigma_name is not None:
-        sig, sig_names, _ = _posterior_columns(data, [sigma_name])
-        if sig.shape[1] != 1:
-            raise ValueError(f"sigma_name must name a scalar variable, '{sigma_name}' has {sig.shape[1]} entries per draw")
-        sigma = sig[:, 0]
+    per_draw = {}
+    for what, name in (("sigma_name", sigma_name), ("phi_name", phi_name), ("shape_name", shape_name)):
+        per_draw[what] = None
+        if name is not None:
+            col, _, _ = _posterior_columns(data, [name])
+            if col.shape[1] != 1:
+                raise ValueError(f"{what} must name a scalar variable, '{name}' has {col.shape[1]} entries per draw")
+            per_draw[what] = col[:, 0]
     if y is None:
         if var_name is None or not hasattr(data, "observed_data"):
             raise ValueError("y=None needs var_name and an observed_data group")
@@ -295,19 +355,20 @@ def loo_glm(idata, X, y, family, var_names, sigma_name=None, var_name=None, offs
                 raise ValueError(f"group_terms[{t}] must be (name, index) or (name, index, z)")
             draws, _, _ = _posterior_columns(data, [term[0]])
             groups.append((term[1], draws, *term[2:]))
-    return loo_glm_from_design(X, y, beta, family, sigma=sigma, offset=offset, trials=trials, reff=reff, scale=scale, method=method,
-                               pointwise=pointwise, rows=rows, groups=groups)
+    return loo_glm_from_design(X, y, beta, family, sigma=per_draw["sigma_name"], offset=offset, trials=trials, reff=reff, scale=scale,
+                               method=method, pointwise=pointwise, rows=rows, groups=groups, phi=per_draw["phi_name"],
+                               shape=per_draw["shape_name"], link=link)
 
 
 def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="plpd", estimator="diff_srs",
                       loo_approximation_draws=None, sigma=None, offset=None, trials=None, reff=1.0, scale=None, pointwise=False,
-                      groups=None):
+                      groups=None, *, phi=None, shape=None, link=None):
     """Subsampled PSIS-LOO (Magnusson et al. 2019, 2020) of a GLM without its matrix.  The approximation for ALL observations is
     ``"plpd"`` -- ``glm_plpd``, the log-likelihood at the posterior mean -- or ``"lpd"``, the ``lppd_i`` of a fused pass over
     (thinned) draws; the subsample is drawn by ``subsample_indices``; only the ``m`` sampled rows of the matrix are generated
     (``glm_log_lik(rows=idx)``) and go through PSIS-LOO and the variance over draws.  Estimators, warnings and result layout are
-    those of ``loo_subsample_from_matrix``.  ``groups``: the group-level terms of a multilevel model (the module's text).  Returns
-    ``(ELPDData, SubsampleIndices, Estimate)``."""
+    those of ``loo_subsample_from_matrix``.  ``groups``: the group-level terms of a multilevel model (the module's text).  ``phi``,
+    ``shape``, ``link``: as ``glm_log_lik`` takes them.  Returns ``(ELPDData, SubsampleIndices, Estimate)``."""
     kind = str(loo_approximation).lower()
     if kind not in ("plpd", "lpd"):
         raise ValueError(f"Invalid loo_approximation '{loo_approximation}'. Must be one of: plpd, lpd (of {', '.join(APPROXIMATIONS)})")
@@ -316,7 +377,7 @@ def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="p
         raise ValueError(f"Invalid estimator '{estimator}'. Must be one of: {', '.join(ESTIMATORS)}")
     scale, scale_value = _scale_value(scale)
     reff = _check_reff(reff)
-    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
+    Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials, phi, shape, link)
     terms = _prepare_groups(groups, Xc, bc.shape[0])
     n_data_points, n_samples = Xc.shape[0], bc.shape[0]
     if isinstance(observations, (int, np.integer)) and not isinstance(observations, bool):
@@ -340,9 +401,9 @@ def loo_subsample_glm(X, y, beta, family, observations=100, loo_approximation="p
         raise ValueError(f"Requested {loo_approximation_draws} draws but only {n_samples} are available")
 
     eng = _engine_of(Xc)
-    fam = _ENGINE_FAMILY[family]
+    fam = _engine_family(family, link)
     if kind == "plpd":
-        b1, v1 = _posterior_mean(bc, v)
+        b1, v1 = _posterior_mean(bc, v, family)
         approx = _to_host(eng.glm(Xc, b1, fam, **v1, **_with_groups(_groups_at(terms, _mean_draw)))).reshape(-1).astype(np.float64)
     else:
         bt, vt, tt = bc, v, terms

@@ -29,7 +29,7 @@ import numpy as np
 from .base import ISMethod, parse_method, tail_count_for
 from .engine import _is_torch_tensor
 from .loo import _scale_value
-from .loo_glm import _ENGINE_FAMILY, _all, _check_reff, _engine_of, _prepare, _prepare_groups, _with_groups
+from .loo_glm import _ENGINE_FAMILY, _all, _engine_family, _check_reff, _engine_of, _prepare, _prepare_groups, _with_groups
 from .loo_group import _diagnostic_warning, _logo_array, _method_warning, _nan_warning, _pack, _summaries, group_index
 from .loo_influence import _posterior_columns
 from .loo_subsample import _to_host
@@ -124,25 +124,34 @@ def _prepare_marginal(X, n_draws, cluster, tau, z, u, loc, scale, n_nodes, group
     return index, tau, z, nodes, logw
 
 
-def _setup(X, y, beta, family, cluster, tau, z, u, loc, scale, n_nodes, sigma, offset, trials, groups):
+MARGINAL_FAMILIES = ("gaussian", "bernoulli", "binomial", "poisson")
+
+
+def _setup(X, y, beta, family, cluster, tau, z, u, loc, scale, n_nodes, sigma, offset, trials, groups, link=None):
+    if family in ("negbinomial", "gamma") or link == "probit":
+        what = f"the {family} family" if link != "probit" else "the probit link"
+        raise ValueError(f"the cluster-marginal pass takes the families {', '.join(MARGINAL_FAMILIES)} with their canonical links, "
+                         f"not {what}")
     Xc, bc, v = _prepare(X, y, beta, family, sigma, offset, trials)
     terms = _prepare_groups(groups, Xc, bc.shape[0])
+    _engine_family(family, link)
     index, tau, z, nodes, logw = _prepare_marginal(Xc, bc.shape[0], cluster, tau, z, u, loc, scale, n_nodes, terms)
     return Xc, bc, v, terms, index, dict(tau=tau, z=z, nodes=nodes, log_weights=logw)
 
 
 def glm_marginal_log_lik(X, y, beta, family, cluster, tau, z=None, u=None, loc=None, scale=None, n_nodes=15, sigma=None, offset=None,
-                         trials=None, groups=None):
+                         trials=None, groups=None, *, link=None):
     """The ``(C, S)`` marginal log-likelihood of the clusters of ``cluster`` [N] (integer labels), rows in the order of
     ``group_index(cluster).labels``.  ``tau`` [S]: the scale of the integrated effect per draw; ``z`` [N]: its covariate (None: an
     intercept); ``u`` (S, C): its draws, which centre the nodes -- or ``loc`` / ``scale`` [C] (the module's text); ``groups``: the
-    conditional terms of ``loo_glm``, held at their draws.  torch on the device for a CUDA ``X``, NumPy otherwise."""
-    Xc, bc, v, terms, index, q = _setup(X, y, beta, family, cluster, tau, z, u, loc, scale, n_nodes, sigma, offset, trials, groups)
+    conditional terms of ``loo_glm``, held at their draws; ``link``: None or the canonical link of the family (the probit link,
+    like the negative binomial and gamma families, is not integrated here).  torch on the device for a CUDA ``X``, NumPy otherwise."""
+    Xc, bc, v, terms, index, q = _setup(X, y, beta, family, cluster, tau, z, u, loc, scale, n_nodes, sigma, offset, trials, groups, link)
     return _engine_of(Xc).glm_marginal(Xc, bc, _ENGINE_FAMILY[family], index, **q, **v, **_with_groups(terms))
 
 
 def loo_glm_marginal_from_design(X, y, beta, family, cluster, tau, z=None, u=None, loc=None, node_scale=None, n_nodes=15, sigma=None,
-                                 offset=None, trials=None, groups=None, reff=1.0, scale=None, method="psis", pointwise=False):
+                                 offset=None, trials=None, groups=None, reff=1.0, scale=None, method="psis", pointwise=False, *, link=None):
     """Leave-one-cluster-out PSIS-LOO on the marginal likelihood in one fused pass: per block of members the linear predictor is
     generated into a bounded buffer, turned into rows of ``mll`` and consumed by the LOO kernels.  Returns the ``ELPDData`` of
     ``loo_group_from_matrix`` on ``glm_marginal_log_lik(...)`` with one group per row -- the same keys, warnings and texts.
@@ -150,7 +159,8 @@ def loo_glm_marginal_from_design(X, y, beta, family, cluster, tau, z=None, u=Non
     method = parse_method(method)
     scale, scale_value = _scale_value(scale)
     reff = _check_reff(reff)
-    Xc, bc, v, terms, index, q = _setup(X, y, beta, family, cluster, tau, z, u, loc, node_scale, n_nodes, sigma, offset, trials, groups)
+    Xc, bc, v, terms, index, q = _setup(X, y, beta, family, cluster, tau, z, u, loc, node_scale, n_nodes, sigma, offset, trials, groups,
+                                        link)
     n_samples = bc.shape[0]
     if n_samples < 2:
         raise ValueError("PSIS-LOO needs at least two draws")
@@ -172,7 +182,7 @@ def loo_glm_marginal_from_design(X, y, beta, family, cluster, tau, z=None, u=Non
 
 
 def loo_glm_marginal(idata, X, y, family, var_names, cluster, u_name, tau_name, z=None, n_nodes=15, sigma_name=None, var_name=None,
-                     offset=None, trials=None, group_terms=None, reff=1.0, scale=None, method="psis", pointwise=False):
+                     offset=None, trials=None, group_terms=None, reff=1.0, scale=None, method="psis", pointwise=False, *, link=None):
     """``loo_glm_marginal_from_design`` with the draws taken from ``idata``: ``beta`` from ``var_names`` as ``loo_glm`` takes it,
     the draws of the integrated effect from ``u_name`` (shape ``(chain, draw, C)``, one entry per cluster in the order of its sorted
     labels; None: nodes from ``mean(tau)``) and its scale from the scalar ``tau_name``.  ``group_terms``, ``sigma_name`` and
@@ -205,4 +215,5 @@ def loo_glm_marginal(idata, X, y, family, var_names, cluster, u_name, tau_name, 
             draws, _, _ = _posterior_columns(data, [term[0]])
             groups.append((term[1], draws, *term[2:]))
     return loo_glm_marginal_from_design(X, y, beta, family, cluster, tau, z=z, u=u, n_nodes=n_nodes, sigma=sigma, offset=offset,
-                                        trials=trials, groups=groups, reff=reff, scale=scale, method=method, pointwise=pointwise)
+                                        trials=trials, groups=groups, reff=reff, scale=scale, method=method, pointwise=pointwise,
+                                        link=link)

@@ -3,6 +3,7 @@
 
     python tools/bench_loo_glm.py [--obs N] [--draws S] [--predictors 4,16,64] [--families gaussian,binomial,poisson] [--steps K]
                                   [--warmup W] [--big-obs 4000000] [--big-predictors 16] [--out profiles/loo_glm_bench]
+(--families takes the engine's names: also negbinomial, gamma, binomial_probit)
 
 One step = Engine.glm(mode="loo"): the image of beta once, then per block of observations the GLM kernel into the engine's block
 buffer and the PSIS-LOO pass on the block (pla_glm).  Reported per (family, P), each as the MEDIAN wall time of --steps synchronised
@@ -72,6 +73,21 @@ def make_model(torch, N, S, P, family, seed):
         v["trials"] = torch.full((N,), 10.0, dtype=torch.float64, device="cuda")
         v["y"] = torch.binomial(v["trials"], torch.sigmoid(eta0), generator=gen)
         v["obs_const"] = torch.lgamma(v["trials"] + 1.0) - torch.lgamma(v["y"] + 1.0) - torch.lgamma(v["trials"] - v["y"] + 1.0)
+    elif family == "binomial_probit":
+        v["trials"] = torch.full((N,), 10.0, dtype=torch.float64, device="cuda")
+        v["y"] = torch.binomial(v["trials"], torch.special.ndtr(eta0), generator=gen)
+        v["obs_const"] = torch.lgamma(v["trials"] + 1.0) - torch.lgamma(v["y"] + 1.0) - torch.lgamma(v["trials"] - v["y"] + 1.0)
+    elif family == "negbinomial":  # NB2 with phi near 2: a gamma mixture of Poissons
+        a = v["draw_scale"] = 2.0 * torch.exp(0.2 * rn(S))
+        v["draw_const"] = a * torch.log(a) - torch.lgamma(a)
+        rate = torch.distributions.Gamma(torch.full((N,), 2.0, dtype=torch.float64, device="cuda"), 2.0 / torch.exp(eta0)).sample()
+        v["y"] = torch.poisson(rate, generator=gen)
+        v["obs_const"] = -torch.lgamma(v["y"] + 1.0)
+    elif family == "gamma":  # shape near 3, mean exp(eta)
+        a = v["draw_scale"] = 3.0 * torch.exp(0.2 * rn(S))
+        v["draw_const"] = a * torch.log(a) - torch.lgamma(a)
+        v["y"] = torch.distributions.Gamma(torch.full((N,), 3.0, dtype=torch.float64, device="cuda"), 3.0 / torch.exp(eta0)).sample()
+        v["obs_const"] = torch.log(v["y"])
     else:
         v["y"] = torch.poisson(torch.exp(eta0), generator=gen)
         v["obs_const"] = -torch.lgamma(v["y"] + 1.0)
@@ -85,6 +101,15 @@ def formula(torch, family, eta, v):
     if family == "binomial":
         sp = torch.clamp(eta, min=0.0) + torch.log1p(torch.exp(-eta.abs()))
         return v["obs_const"][:, None] + y * eta - v["trials"][:, None] * sp
+    if family == "binomial_probit":
+        return v["obs_const"][:, None] + y * torch.special.log_ndtr(eta) + (v["trials"][:, None] - y) * torch.special.log_ndtr(-eta)
+    if family == "negbinomial":
+        a = v["draw_scale"][None, :]
+        L = torch.logaddexp(eta, torch.log(a))
+        return v["obs_const"][:, None] + v["draw_const"][None, :] + torch.lgamma(y + a) + y * eta - (y + a) * L
+    if family == "gamma":
+        a = v["draw_scale"][None, :]
+        return v["draw_const"][None, :] + (a - 1.0) * v["obs_const"][:, None] - a * (eta + y * torch.exp(-eta))
     return v["obs_const"][:, None] + y * eta - torch.exp(eta)
 
 
