@@ -70,10 +70,11 @@ static int group_sums_run(pla_engine* eng, const void* ll, int dtype, int64_t n_
                           int64_t stride_draw, const int64_t* d_off, const int64_t* d_mem, int64_t n_groups, int64_t g0, int64_t ng,
                           int mem_space, hipStream_t s, void* out, unsigned long long* replaced) {
   const size_t esz = dtype == PLA_F64 ? 8 : 4;
+  const char* leg = "";  // the vector leg of the (last) launch: "16-byte loads" / "element loads"
   if (mem_space == PLA_DEVICE && stride_draw == 1) {
     PLA_HIP(pla::launch_group_sum(ll, dtype, stride_obs, 0, n_obs, n_obs, false, true, (int)n_draws, d_off, d_mem, n_groups, g0, ng,
-                                  out, replaced, s));
-    eng->last_kernels = "group_sum_kernel (matrix read in place)";
+                                  out, replaced, s, &leg));
+    eng->last_kernels = std::string("group_sum_kernel (matrix read in place; ") + leg + ")";
     return PLA_OK;
   }
   const bool obs_fastest = n_obs > 1 && n_draws > 1 && stride_obs == 1 && stride_draw >= n_obs;
@@ -93,11 +94,12 @@ static int group_sums_run(pla_engine* eng, const void* ll, int dtype, int64_t n_
       if (rc) return rc;
     }
     PLA_HIP(pla::launch_group_sum(eng->d_in.p, dtype, n_draws, r0, nr, n_obs, blocked, r0 == 0, (int)n_draws, d_off, d_mem, n_groups, g0,
-                                  ng, out, replaced, s));
+                                  ng, out, replaced, s, &leg));
     if (mem_space == PLA_HOST) PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next block
   }
-  eng->last_kernels = mem_space == PLA_DEVICE ? "transpose_rows_kernel + group_sum_kernel (blocks of observations)"
-                                              : "group_sum_kernel (blocks of observations uploaded)";
+  // (every block has the staging buffer's base and pitch: one leg for all of them)
+  eng->last_kernels = std::string(mem_space == PLA_DEVICE ? "transpose_rows_kernel + group_sum_kernel (blocks of observations; "
+                                                          : "group_sum_kernel (blocks of observations uploaded; ") + leg + ")";
   return PLA_OK;
 }
 

@@ -38,10 +38,14 @@ static hipError_t launch_gather_typed(GatherParams p, hipStream_t stream, const 
     const size_t with_idx = row_bytes + (size_t)p.n_out * sizeof(int);
     if (with_idx <= (size_t)kGatherLdsBytes) {
       p.idx_off = (int)row_bytes;
-      if (route) *route = "gather_draws_kernel<lds+index> (draws fastest: row and index staged in LDS)";
+      if (route)
+        *route = wide ? "gather_draws_kernel<lds+index> (draws fastest: row and index staged in LDS; 16-byte loads)"
+                      : "gather_draws_kernel<lds+index> (draws fastest: row and index staged in LDS; element loads)";
       return wide ? launch_gather_lds<T, kGatherLdsIdx, kVec>(p, with_idx, stream) : launch_gather_lds<T, kGatherLdsIdx, 1>(p, with_idx, stream);
     }
-    if (route) *route = "gather_draws_kernel<lds> (draws fastest: row staged in LDS, index from global memory)";
+    if (route)
+      *route = wide ? "gather_draws_kernel<lds> (draws fastest: row staged in LDS, index from global memory; 16-byte loads)"
+                    : "gather_draws_kernel<lds> (draws fastest: row staged in LDS, index from global memory; element loads)";
     return wide ? launch_gather_lds<T, kGatherLds, kVec>(p, row_bytes, stream) : launch_gather_lds<T, kGatherLds, 1>(p, row_bytes, stream);
   }
   if (route) *route = "gather_draws_kernel<global> (gathered straight from global memory)";

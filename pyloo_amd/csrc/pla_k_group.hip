@@ -30,14 +30,16 @@ static hipError_t launch_group_sum_typed(GroupSumParams p, int64_t n_groups, hip
 
 hipError_t launch_group_sum(const void* in, int dtype, int64_t stride_obs, int64_t row0, int64_t n_rows, int64_t n_src, bool blocked,
                             bool first_block, int n_draws, const int64_t* offsets, const int64_t* members, int64_t n_groups_total,
-                            int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream) {
-  if (n_groups <= 0 || n_draws <= 0) return hipSuccess;
-  GroupSumParams p{in, stride_obs, row0, n_rows, n_src, blocked, first_block, n_draws, offsets, members, n_groups_total, g0, 0, out,
-                   replaced};
+                            int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream,
+                            const char** route) {
   // 16-byte loads and stores where every row and every output row starts on a 16-byte boundary
   const size_t esz = dtype == PLA_F64 ? 8 : 4;
   const int vec = (int)(16 / esz);
   const bool wide = (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0 && stride_obs % vec == 0 && n_draws % vec == 0;
+  if (route) *route = wide ? "16-byte loads" : "element loads";
+  if (n_groups <= 0 || n_draws <= 0) return hipSuccess;
+  GroupSumParams p{in, stride_obs, row0, n_rows, n_src, blocked, first_block, n_draws, offsets, members, n_groups_total, g0, 0, out,
+                   replaced};
   if (dtype == PLA_F64)
     return wide ? launch_group_sum_typed<double, 2>(p, n_groups, stream) : launch_group_sum_typed<double, 1>(p, n_groups, stream);
   return wide ? launch_group_sum_typed<float, 4>(p, n_groups, stream) : launch_group_sum_typed<float, 1>(p, n_groups, stream);

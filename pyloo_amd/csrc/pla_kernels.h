@@ -121,10 +121,12 @@ hipError_t launch_waic_col(const void* in, int dtype, int64_t n_obs, int n_draws
                            double* var_i, double* waic_i, unsigned long long* replaced, hipStream_t stream);
 // group sums of the leave-one-group-out pass (pla_group.h): out[g - g0, s] = sum of ll[m, s] over the members of group g in
 // ascending order (NumPy's order), groups [g0, g0 + n_groups); the rows come from `in` = observations [row0, row0 + n_rows) of the
-// matrix, draws contiguous (blocked: one of several blocks, partial sums continued in `out`).  replaced: NaN entries (may be null)
+// matrix, draws contiguous (blocked: one of several blocks, partial sums continued in `out`).  replaced: NaN entries (may be null).
+// *route (may be null): the vector leg taken, "16-byte loads" or "element loads", for pla_engine_last_kernels.
 hipError_t launch_group_sum(const void* in, int dtype, int64_t stride_obs, int64_t row0, int64_t n_rows, int64_t n_src, bool blocked,
                             bool first_block, int n_draws, const int64_t* offsets, const int64_t* members, int64_t n_groups_total,
-                            int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream);
+                            int64_t g0, int64_t n_groups, void* out, unsigned long long* replaced, hipStream_t stream,
+                            const char** route);
 // draw gather of the approximate-posterior pass (pla_draws.h): out[i, j] = in[i * stride_obs + clamp(draw_index[j]) * stride_draw] for
 // the n_rows rows at `in`, out a contiguous (n_rows, n_out) block; NaN -> -1e10, counted in `replaced` (may be null).  *route (may be
 // null): text for pla_engine_last_kernels.  Rows of at most gather_lds_max_draws(dtype) draws are staged in LDS.
