@@ -789,7 +789,8 @@ int pla_glm_marginal_segment(void); /* L of the summation rule */
  *             elpd_i[j] = logsumexp_s(lw_j + f_j) - logsumexp_s(lw_j)
  * All arithmetic is f64 (f32 input is widened on load); NaN entries of ll count as -1e10 and are counted in *n_replaced (pla_lfo:
  * every entry of rows [first, first + n_steps + horizon - 1) once; pla_lfo_ratios: of rows [first, first + n_steps - 1)); +-inf are
- * kept.  A weight of log -inf is 0; a step whose weights are all NaN gives NaN.
+ * kept.  A weight of log -inf is 0; a step whose weights are all NaN gives NaN, and so does a step for which lw_j + f_j is -inf at
+ * every draw (an observation of likelihood 0 under every draw: logsumexp of nothing), whatever n_draws -- never -inf.
  *
  * THE SUMMATION RULE of lr.  With the chunk length C = 64, per draw, every sum taken in the order written:
  *     total[c] = ll[first + cC] + ll[first + cC + 1] + ... + ll[first + cC + C - 1]        carry[0] = 0, carry[c + 1] = carry[c] + total[c]

@@ -26,8 +26,10 @@
 // den = sum exp(lw - max lw), then a = lw + f in place with the M future rows read in place through the matrix's row stride, max a, and
 // num = sum exp(a - max a).  Longer rows are streamed once with a running maximum per lane (the sums are rescaled when it moves;
 // the lanes are merged at the end).  elpd = (max a + log num) - (max lw + log den).  lw = -inf carries weight 0; a step whose
-// weights are all NaN gives NaN.  NaN entries of ll are counted once each over a pass: every step counts the last row of its
-// window, step 0 of the pass the whole of it.
+// weights are all NaN gives NaN, and so does a step no draw of which has a finite a (every a = -inf: an observation of likelihood
+// 0 under every draw) -- ON BOTH ROUTES: in registers exp(-inf - -inf) is NaN by itself, the streamed route skips a = -inf terms
+// and says so at the end.  NaN entries of ll are counted once each over a pass: every step counts the last row of its window,
+// step 0 of the pass the whole of it.
 //
 // lfo_first_high_kernel: the smallest j >= 1 with k_j > k_threshold (n_steps when there is none; NaN is not above), one workgroup,
 // an integer atomic min in LDS.
@@ -394,6 +396,7 @@ __global__ __launch_bounds__(kWave * kLfoWaves) __attribute__((amdgpu_waves_per_
       m_a = wave_reduce<OpMax>(ma);
       den = ml == -pinf() ? den : den * exp(ml - m_lw);  // (a lane without a finite weight holds 0, or NaN from a NaN weight)
       num = ma == -pinf() ? num : num * exp(ma - m_a);
+      num = m_a == -pinf() ? m_a - m_a : num;  // (no draw has a finite a: NaN, the register route's exp(-inf - -inf); wave-uniform)
     }
     den = wave_reduce<OpSum>(den);
     num = wave_reduce<OpSum>(num);

@@ -285,6 +285,7 @@ __global__ __launch_bounds__(kWave * kLfoWaves) __attribute__((amdgpu_waves_per_
       m_a = wave_reduce<OpMax>(ma);
       den = ml == -pinf() ? den : den * exp(ml - m_lw);  // (a lane without a finite weight holds 0, or NaN from a NaN weight)
       num = ma == -pinf() ? num : num * exp(ma - m_a);
+      num = m_a == -pinf() ? m_a - m_a : num;  // (no draw has a finite a: NaN, the register route's exp(-inf - -inf); wave-uniform)
     }
     den = wave_reduce<OpSum>(den);
     num = wave_reduce<OpSum>(num);
