@@ -780,6 +780,57 @@ int pla_glm_marginal(const pla_glm_marginal_args *args);
 int pla_glm_marginal_segment(void); /* L of the summation rule */
 
 /*
+ * Leave-one-out predictive moments and LOO-PIT of a GLM without predictive draws and without the matrix (csrc/pla_glm_predict.h).
+ * Given eta[i, s] (pla_glm's, bit for bit) and the per-draw value, the conditional mean mu, variance v and distribution function F
+ * of y_i are closed forms, so with lw row i of the log weights, m = max_s lw_s and e_s = exp(lw_s - m) (a weight of log -inf is 0
+ * and its draw contributes to nothing):
+ *     mean[i]   = sum_s e_s mu_is / sum e                  E_loo[y_i]
+ *     m2[i]     = sum_s e_s (v_is + mu_is^2) / sum e       the raw second moment (variance = max(m2 - mean^2, 0))
+ *     pit_le[i] = sum_s e_s P(Y <= y_i | draw s) / sum e   pit_lt[i] = sum_s e_s P(Y < y_i | draw s) / sum e
+ *     family                   mu        v                    F
+ *     PLA_GLM_GAUSSIAN         eta       sigma^2              Phi((y - eta) / sigma) from erfcx, pit_lt == pit_le bit for bit
+ *     PLA_GLM_BINOMIAL_LOGIT   n p       n p (1 - p)          p = logistic(eta)        } the downward product recurrence from
+ *     PLA_GLM_BINOMIAL_PROBIT  n p       n p (1 - p)          p = Phi(eta)             } pmf(y) = exp(ll): F_lt = pmf(y) T,
+ *     PLA_GLM_POISSON_LOG      exp(eta)  mu                                            } F_le = min(F_lt + pmf(y), 1),
+ *     PLA_GLM_NEGBINOMIAL_LOG  exp(eta)  mu + mu^2 / phi                               } T = sum_j prod_{k > y - j} pmf(k-1)/pmf(k)
+ *     PLA_GLM_GAMMA_LOG        exp(eta)  mu^2 / alpha         none: a non-NULL pit_le or pit_lt is PLA_ERR_UNSUPPORTED
+ * (F_le = 1 exactly for a binomial count y = n.)  The rounding order of every formula is stated in csrc/pla_glm_predict.h.  A count y outside [0, 4096] is not walked: the row's
+ * two PIT values are NaN and the row is counted in *n_pit_skipped; its moments are computed.  A row whose weights are all -inf
+ * gives NaN.
+ * THE SUMMATION RULE.  With L = pla_glm_predict_segment(), segment k holds the draws [16 L k, 16 L (k + 1)); inside a segment
+ * column c = s mod 16 adds its draws in ascending order from zero, the 16 columns combine by the butterfly c ^ 1, c ^ 2, c ^ 4,
+ * c ^ 8, and the segment sums are added in order of k from segment 0's.  No floating-point atomics: a row's outputs depend on its
+ * row of x, its entries of the vectors, its row of weights and n_draws alone -- not on the grid, the block size
+ * (PLA_INGEST_BLOCK_MB), the memory space, the position of the row or the row list.
+ *
+ * Set struct_size = sizeof(pla_glm_predict_args) and glm.struct_size = sizeof(pla_glm_args); another size is PLA_ERR_ARG.
+ *   glm                 the argument block of pla_glm: engine, family (PLA_GLM_LINPRED: PLA_ERR_ARG), x, beta, the vectors, row_index
+ *                       / n_rows, mem_space and stream as there (n_draws >= 2); method and tail_count as pla_importance_weights takes
+ *                       them (PLA_PIT_LOGLIK).  mode, scale_value, good_k and the block's own outputs are not read.
+ *   kind                PLA_PIT_LOGLIK: per block of rows the generator writes the log-likelihood into engine memory, the pipeline of
+ *                       pla_loo_diag runs on it (-ll with NaN -> -1e10 counted in *n_replaced, the weights pass, Pareto k or the ESS
+ *                       into diag, elpd_i) and the predictive kernel consumes the block's weights before the next block.
+ *                       PLA_PIT_LOG_WEIGHTS: log_weights is (m, n_draws), m the rows of the call, of any normalisation, row stride
+ *                       lw_stride_obs and unit draw stride (another lw_stride_draw: PLA_ERR_UNSUPPORTED); the predictive kernel
+ *                       alone, device weights read in place, host weights staged in blocks; diag and elpd_i are not written,
+ *                       *n_replaced is 0.
+ *   mean, m2, pit_le, pit_lt, diag, elpd_i      [m], each may be NULL;  n_replaced, n_pit_skipped: one int64 each, may be NULL
+ * PLA_DEVICE: everything is enqueued on glm.stream and nothing is allocated once the workspace fits.  PLA_HOST: the call returns
+ * when the results are there.  Engine memory beyond pla_glm's: 8 (1 + 5 ceil(n_draws / (16 L))) bytes per row of a block.
+ */
+typedef struct pla_glm_predict_args {
+  int64_t struct_size;
+  pla_glm_args glm;
+  int64_t kind;
+  const double *log_weights;
+  int64_t lw_stride_obs, lw_stride_draw;
+  double *mean, *m2, *pit_le, *pit_lt, *diag, *elpd_i;
+  int64_t *n_replaced, *n_pit_skipped;
+} pla_glm_predict_args;
+int pla_glm_predict(const pla_glm_predict_args *args);
+int pla_glm_predict_segment(void); /* L of the summation rule */
+
+/*
  * PSIS leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020; forward mode, `horizon` steps ahead; csrc/pla_lfo.h).
  * The observations (rows of ll) are in time order and ll is the log-likelihood of ALL n_obs of them under the draws of one fit to
  * the first `first`.  Step j = 0 .. n_steps - 1 conditions on rows [0, first + j) and predicts rows [first + j, first + j + horizon):

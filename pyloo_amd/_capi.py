@@ -39,7 +39,7 @@ SYMBOLS = (
     "pla_mixis_draw_lse", "pla_mixis_loo", "pla_engine_set_mixis_grid", "pla_mixis_tile_rows",
     "pla_loo_pit", "pla_lfo_ratios", "pla_lfo",
     "pla_loo_diag", "pla_loo_diag_weights", "pla_loo_influence", "pla_glm", "pla_glm_grouped",
-    "pla_glm_marginal", "pla_glm_marginal_segment",
+    "pla_glm_marginal", "pla_glm_marginal_segment", "pla_glm_predict", "pla_glm_predict_segment",
     "pla_relative_eff", "pla_engine_set_ess_grid", "pla_ess_lds_max_draws",
 )
 
@@ -135,6 +135,22 @@ class GlmMarginalArgs(C.Structure):
         self.grouped.glm.struct_size = C.sizeof(GlmArgs)
 
 
+class GlmPredictArgs(C.Structure):
+    """``pla_glm_predict_args`` of include/pyloo_amd.h: ``glm`` is a ``GlmArgs`` (both ``struct_size`` are set on construction)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int64), ("glm", GlmArgs), ("kind", C.c_int64), ("log_weights", C.c_void_p),
+        ("lw_stride_obs", C.c_int64), ("lw_stride_draw", C.c_int64),
+        ("mean", C.c_void_p), ("m2", C.c_void_p), ("pit_le", C.c_void_p), ("pit_lt", C.c_void_p), ("diag", C.c_void_p),
+        ("elpd_i", C.c_void_p), ("n_replaced", C.c_void_p), ("n_pit_skipped", C.c_void_p),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(GlmPredictArgs)
+        self.glm.struct_size = C.sizeof(GlmArgs)
+
+
 class EngineError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -225,6 +241,8 @@ def load_library():
     lib.pla_glm_grouped.argtypes = [C.POINTER(GlmGroupedArgs)]
     lib.pla_glm_marginal.argtypes = [C.POINTER(GlmMarginalArgs)]
     lib.pla_glm_marginal_segment.argtypes = []
+    lib.pla_glm_predict.argtypes = [C.POINTER(GlmPredictArgs)]
+    lib.pla_glm_predict_segment.argtypes = []
     lib.pla_lfo_ratios.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp]
     lib.pla_lfo.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, ci, i64, dbl, ci, vp, vp, vp, vp, vp]
     lib.pla_relative_eff.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, ci, ci, vp, vp, vp]

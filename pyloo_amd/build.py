@@ -27,6 +27,7 @@ SOURCES = [
     "pla_k_nonfactor.hip", "pla_k_draws.hip", "pla_k_kfold.hip", "pla_k_mm.hip", "pla_k_mixis.hip", "pla_k_pit.hip", "pla_k_lfo.hip",
     "pla_k_lfo_bw.hip", "pla_k_ess.hip", "pla_k_diag.hip", "pla_k_influence.hip", "pla_k_glm.hip",
     "pla_k_glm_terms.hip", "pla_k_glm_marginal.hip", "pla_k_glm_families.hip", "pla_k_glm_terms_families.hip",
+    "pla_k_glm_predict.hip", "pla_k_glm_predict_families.hip",
     "pla_capi_core.hip", "pla_capi_loo.hip", "pla_capi_views.hip", "pla_capi_passes.hip", "pla_capi_models.hip", "pla_capi_glm.hip",
 ]
 PUBLIC_HEADER = os.path.join(HERE, "..", "include", "pyloo_amd.h")

@@ -5,7 +5,8 @@
 //   pla_capi_views.hip   groups, draw gather, k-fold
 //   pla_capi_passes.hip  LOO-PIT, diagnostics, influence, leave-future-out, relative efficiency, Mix-IS
 //   pla_capi_models.hip  comparison / stacking / bootstrap, moment matching, non-factorised LOO
-//   pla_capi_glm.hip     GLM log-likelihood generator and its fused PSIS-LOO pass; the cluster-marginal likelihood on top of it
+//   pla_capi_glm.hip     GLM log-likelihood generator and its fused PSIS-LOO pass; the cluster-marginal likelihood on top of it; the
+//                        leave-one-out predictive moments and PIT of the model
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -112,6 +113,7 @@ struct pla_engine {
   Buffer d_glm_u;   // ... pla_glm_grouped alone (pla_glm_terms.h): the image of the group effects; behind it the group indices, z and u of a host call
   Buffer d_glm_marg;  // ... pla_glm_marginal alone (pla_glm_marginal.h): segment and join tables, the carry, the partial sums; behind them z, tau, nodes and log_weights of a host call
   Buffer d_glm_mll;   // ... and its block of finished clusters (the fused LOO pass; the matrix mode of a host call)
+  Buffer d_glm_pred;  // ... pla_glm_predict alone (pla_glm_predict.h): the row maxima of a block's weights and its per-(row, segment) partial sums
 
   // ... the k-fold table's pinned host copy (the upload reads it after the call has returned), two of them used in turn, and the
   // event behind each upload: a call waits for the upload of the call before the previous one before it rewrites that copy

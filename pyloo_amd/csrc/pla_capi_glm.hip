@@ -5,6 +5,8 @@
 // pla_glm_marginal integrates one effect per cluster out of the likelihood (csrc/pla_glm_marginal.h): the generator writes the linear
 // predictor of a block of members, the marginal kernels turn it into rows of the (n_clusters, n_draws) matrix; the segment tables,
 // the partial sums and the carry, d_glm_marg, and the block of finished clusters, d_glm_mll, are its buffers alone.
+// pla_glm_predict contracts the generator's tile against a block of leave-one-out weights instead of storing it
+// (csrc/pla_glm_predict.h): the predictive moments and PIT; the row maxima and the partial sums, d_glm_pred, are its buffer alone.
 // Host code only: argument checks, uploads of a PLA_HOST call, kernel launches on the caller's stream.
 #include "pla_capi.h"
 #include "pla_glm_marginal.h"
@@ -617,6 +619,153 @@ int marg_run(const pla_glm_marginal_args* a) {
   return PLA_OK;
 }
 
+// ---- pla_glm_predict -------------------------------------------------------------------------------------------------------------
+// PLA_PIT_LOGLIK: per block of rows the generator into d_glm_ll, then pla_loo_diag's pipeline on the block as on a resident matrix
+// (-ll into d_in, the weights pass into d_lw, diag_wave_kernel for elpd_i), then the predictive kernel on d_lw before the next block
+// overwrites anything.  PLA_PIT_LOG_WEIGHTS: the predictive kernel alone, on the caller's device weights in place or on blocks of
+// host weights staged in d_lw.  Outputs of a host call in d_pw.
+int predict_run(const pla_glm_predict_args* a) {
+  const bool loglik = a->kind == PLA_PIT_LOGLIK;
+  if (!loglik && a->kind != PLA_PIT_LOG_WEIGHTS) return fail(PLA_ERR_ARG, "bad kind %lld", (long long)a->kind);
+  if (a->glm.family == PLA_GLM_LINPRED) return fail(PLA_ERR_ARG, "pla_glm_predict needs a likelihood, not PLA_GLM_LINPRED");
+  pla_glm_args ga = a->glm;  // as glm_check reads a fused pass: at least two draws; the weights' method and tail count for PLA_PIT_LOGLIK
+  ga.mode = PLA_GLM_MODE_LOO;
+  if (!loglik) ga.method = PLA_SIS;
+  const int64_t m = ga.row_index ? ga.n_rows : ga.n_obs;  // rows of this call
+  int rc = glm_check(&ga, 0, nullptr, ga.row_index, ga.n_rows, m);
+  if (rc) return rc;
+  const bool want_pit = a->pit_le || a->pit_lt;
+  if (ga.family == PLA_GLM_GAMMA_LOG && want_pit)
+    return fail(PLA_ERR_UNSUPPORTED, "PLA_GLM_GAMMA_LOG has no distribution function here: pit_le and pit_lt must be NULL");
+  if (!loglik) {
+    if (m > 0 && !a->log_weights) return fail(PLA_ERR_ARG, "log_weights is NULL");
+    if (a->lw_stride_obs <= 0 || a->lw_stride_draw <= 0) return fail(PLA_ERR_ARG, "log_weights strides must be positive");
+    if (a->lw_stride_draw != 1) return fail(PLA_ERR_UNSUPPORTED, "log_weights need unit stride along the draws");
+    if (m > 1 && a->lw_stride_obs < ga.n_draws) return fail(PLA_ERR_ARG, "lw_stride_obs %lld is less than n_draws", (long long)a->lw_stride_obs);
+  }
+  pla_engine* eng = ga.engine;
+  const bool host = ga.mem_space == PLA_HOST;
+  const int64_t n_draws = ga.n_draws;
+  const int S = (int)n_draws;
+  PLA_ENGINE_CALL(eng, ga.stream);
+  if (m == 0) {
+    for (int64_t* c : {a->n_replaced, a->n_pit_skipped}) {
+      if (host && c) *c = 0;
+      if (!host && c) PLA_HIP(hipMemsetAsync(c, 0, sizeof(int64_t), s));
+    }
+    return PLA_OK;
+  }
+  GlmSetup su;
+  if ((rc = glm_prepare(&ga, ga.family, 0, nullptr, ga.row_index, m, s, &su))) return rc;
+  pla::GlmLaunch& g = su.g;
+
+  // ---- the rows of a block, and for PLA_PIT_LOGLIK its weights pass as pla_importance_weights sets it up
+  pla::RowsParams p{};
+  int64_t rows = staged_chunk_rows(loglik ? PLA_DEVICE : ga.mem_space, true, m, n_draws, sizeof(double));
+  const size_t block_bytes = (size_t)rows * (size_t)n_draws * sizeof(double);
+  if (loglik) {
+    rc = weights_block_setup(eng, ga.method, ga.tail_count, n_draws, sizeof(double), s, &rows, &p);
+    if (!rc) rc = eng->d_glm_ll.reserve(block_bytes);
+    if (!rc) rc = eng->d_in.reserve(block_bytes);
+  } else if (host) {
+    rc = eng->d_lw.reserve(block_bytes);
+  }
+  if (!rc) rc = eng->d_glm_pred.reserve((size_t)pla::glm_predict_workspace(rows, S) * sizeof(double));
+  if (rc) return rc;
+
+  // ---- outputs: the caller's device arrays, or engine memory
+  unsigned long long *d_count = nullptr, *d_skipped = nullptr;
+  double *d_mean = a->mean, *d_m2 = a->m2, *d_le = a->pit_le, *d_lt = a->pit_lt, *d_diag = loglik ? a->diag : nullptr,
+         *d_elpd = loglik ? a->elpd_i : nullptr;
+  HostOutputs out(eng, s);
+  if (host) {
+    d_count = eng->counters + pla::kCounterGlmReplaced;
+    d_skipped = eng->counters + pla::kCounterGlmPitSkipped;
+    rc = out.reserve(6, m, d_count);
+    if (rc) return rc;
+    PLA_HIP(hipMemsetAsync(d_skipped, 0, sizeof(unsigned long long), s));
+    d_mean = a->mean ? out.col(0) : nullptr;
+    d_m2 = a->m2 ? out.col(1) : nullptr;
+    d_le = a->pit_le ? out.col(2) : nullptr;
+    d_lt = a->pit_lt ? out.col(3) : nullptr;
+    d_diag = loglik && a->diag ? out.col(4) : nullptr;
+    d_elpd = loglik && a->elpd_i ? out.col(5) : nullptr;
+  } else {
+    d_count = a->n_replaced ? (unsigned long long*)a->n_replaced : eng->counters + pla::kCounterGlmReplaced;
+    d_skipped = a->n_pit_skipped ? (unsigned long long*)a->n_pit_skipped : eng->counters + pla::kCounterGlmPitSkipped;
+    PLA_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+    PLA_HIP(hipMemsetAsync(d_skipped, 0, sizeof(unsigned long long), s));
+  }
+
+  char route[200], droute[160];
+  std::string label;
+  for (int64_t r0 = 0; r0 < m; r0 += rows) {
+    const int64_t nr = m - r0 < rows ? m - r0 : rows;
+    g.row_index = su.in.rows ? su.in.rows + r0 : nullptr;
+    g.r_first = r0;
+    g.n_rows = nr;
+    g.out = nullptr;
+    g.pitch = n_draws;
+    g.replaced = nullptr;
+    pla::GlmPredictLaunch q{};
+    const char* prep = "";
+    std::string weights;
+    if (loglik) {
+      char groute[160];
+      g.out = eng->d_glm_ll.as<double>();
+      PLA_HIP(pla::launch_glm(g, s, groute, (int)sizeof(groute)));
+      PLA_HIP(pla::launch_diag_prepare(eng->d_glm_ll.p, PLA_F64, nr, n_draws, 1, nullptr, 0, nr, S, eng->d_in.p, d_count, s, &prep));
+      p.in = eng->d_in.p;
+      p.n_obs = nr;
+      p.diag = d_diag ? d_diag + r0 : nullptr;
+      p.lw_out = eng->d_lw.p;
+      PLA_HIP(pla::launch_rows(p, PLA_F64, true, s));
+      weights = std::string(groute) + " -> " + prep + " -> " + pla::last_rows_kernels() + " -> ";
+      if (d_elpd) {
+        PLA_HIP(pla::launch_diag(eng->d_lw.p, eng->d_in.p, -1.0, PLA_F64, nr, S, n_draws, 1, n_draws, 1, d_elpd + r0, nullptr, nullptr, s, droute,
+                                 (int)sizeof(droute)));
+        weights += std::string(droute) + " -> ";
+      }
+      q.lw = eng->d_lw.as<double>();
+      q.lw_pitch = n_draws;
+    } else if (host) {
+      rc = upload_rows(a->log_weights, nullptr, r0, nr, a->lw_stride_obs, n_draws, sizeof(double), eng->d_lw.p, s);
+      if (rc) return rc;
+      q.lw = eng->d_lw.as<double>();
+      q.lw_pitch = n_draws;
+    } else {
+      q.lw = a->log_weights + (size_t)r0 * (size_t)a->lw_stride_obs;
+      q.lw_pitch = a->lw_stride_obs;
+    }
+    q.work = eng->d_glm_pred.as<double>();
+    q.mean = d_mean ? d_mean + r0 : nullptr;
+    q.m2 = d_m2 ? d_m2 + r0 : nullptr;
+    q.pit_le = d_le ? d_le + r0 : nullptr;
+    q.pit_lt = d_lt ? d_lt + r0 : nullptr;
+    q.skipped = d_skipped;
+    g.out = nullptr;
+    {
+      TimedLaunch t(eng, s);
+      PLA_HIP(pla::launch_glm_predict(g, q, s, route, (int)sizeof(route)));
+    }
+    if (r0 == 0)
+      label = su.prepared + weights + route +
+              (loglik ? " per block of observations" : host ? " (weights staged in blocks)" : " (weights read in place)");
+    if (host && !loglik) PLA_HIP(hipStreamSynchronize(s));  // the staging buffer is reused by the next block
+  }
+  eng->last_kernels = label;
+  if (!host) return PLA_OK;
+  rc = out.copy_back({a->mean, a->m2, a->pit_le, a->pit_lt, loglik ? a->diag : nullptr, loglik ? a->elpd_i : nullptr});
+  if (rc) return rc;
+  unsigned long long h[2] = {0, 0};
+  PLA_HIP(hipMemcpyAsync(&h[0], d_count, sizeof(h[0]), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipMemcpyAsync(&h[1], d_skipped, sizeof(h[1]), hipMemcpyDeviceToHost, s));
+  PLA_HIP(hipStreamSynchronize(s));
+  if (a->n_replaced) *a->n_replaced = (int64_t)h[0];
+  if (a->n_pit_skipped) *a->n_pit_skipped = (int64_t)h[1];
+  return PLA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -655,5 +804,18 @@ int pla_glm_marginal(const pla_glm_marginal_args* a) {
 }
 
 int pla_glm_marginal_segment(void) { return pla::kGlmMargSeg; }
+
+int pla_glm_predict(const pla_glm_predict_args* a) {
+  if (!a) return fail(PLA_ERR_ARG, "args is NULL");
+  if (a->struct_size != (int64_t)sizeof(pla_glm_predict_args))
+    return fail(PLA_ERR_ARG, "struct_size is %lld, pla_glm_predict_args of this library has %lld bytes", (long long)a->struct_size,
+                (long long)sizeof(pla_glm_predict_args));
+  if (a->glm.struct_size != (int64_t)sizeof(pla_glm_args))
+    return fail(PLA_ERR_ARG, "glm.struct_size is %lld, pla_glm_args of this library has %lld bytes", (long long)a->glm.struct_size,
+                (long long)sizeof(pla_glm_args));
+  return predict_run(a);
+}
+
+int pla_glm_predict_segment(void) { return pla::kGlmPredictSeg; }
 
 }  // extern "C"

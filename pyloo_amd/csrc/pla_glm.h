@@ -222,6 +222,29 @@ __device__ __forceinline__ unsigned glm_rolled_epilogue(const GlmParams& P, doub
   return n_nan;
 }
 
+// the MFMA chain of one tile: observations of the lane's row of X (a: its operands, reloaded per panel on the PANEL route) times
+// the 16 draws from s - (s & 15) on, all p_pad predictors in one order, started from zero
+// (shared with the predictive kernel, pla_glm_predict.h: the same chain gives the same bits)
+template <int NCH, bool PANEL>
+__device__ __forceinline__ glm_v4d glm_tile_chain(const GlmParams& P, const double* xr, double (&a)[NCH * 4], int q, int s, int n_panels) {
+  glm_v4d acc = glm_v4d{0.0, 0.0, 0.0, 0.0};
+  const double* bp = P.bimg + (int64_t)s * P.p_pad + 4 * q;
+#pragma unroll 1
+  for (int pn = 0; pn < n_panels; ++pn) {
+    if constexpr (PANEL) glm_load_x<NCH>(xr, P.zero, P.sx_pred, pn * NCH * kGlmK, q, P.n_pred, a);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const double* bc = bp + (pn * NCH + c) * kGlmK;
+      const double2 ba = *reinterpret_cast<const double2*>(bc), bb = *reinterpret_cast<const double2*>(bc + 2);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 0], ba.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 1], ba.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 2], bb.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 3], bb.y, acc, 0, 0, 0);
+    }
+  }
+  return acc;
+}
+
 template <int FAM, int NCH, bool PANEL>
 __global__ __launch_bounds__(kWave * kGlmWaves) void glm_kernel(GlmParams P) {
   const int S = P.n_draws;
@@ -254,21 +277,7 @@ __global__ __launch_bounds__(kWave * kGlmWaves) void glm_kernel(GlmParams P) {
 #pragma unroll 1
     for (int dt = st * P.strip_tiles; dt < t_end; ++dt) {
       const int s = dt * kGlmTile + i;  // this lane's draw: B column and C / D column (s < s_pad)
-      glm_v4d acc = glm_v4d{0.0, 0.0, 0.0, 0.0};
-      const double* bp = P.bimg + (int64_t)s * P.p_pad + 4 * q;
-#pragma unroll 1
-      for (int pn = 0; pn < n_panels; ++pn) {
-        if constexpr (PANEL) glm_load_x<NCH>(xr, P.zero, P.sx_pred, pn * NCH * kGlmK, q, P.n_pred, a);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const double* bc = bp + (pn * NCH + c) * kGlmK;
-          const double2 ba = *reinterpret_cast<const double2*>(bc), bb = *reinterpret_cast<const double2*>(bc + 2);
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 0], ba.x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 1], ba.y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 2], bb.x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[c * 4 + 3], bb.y, acc, 0, 0, 0);
-        }
-      }
+      glm_v4d acc = glm_tile_chain<NCH, PANEL>(P, xr, a, q, s, n_panels);
       // ---- epilogue: C / D col = lane & 15 (the draw), row = (lane >> 4) + 4 reg
       const bool s_ok = s < S;
       double sig = 1.0, dc = 0.0, lsc = 0.0;

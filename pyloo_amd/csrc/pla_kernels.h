@@ -279,6 +279,21 @@ struct GlmTerms {
 int64_t glm_terms_image_size(const GlmTerms& t, int n_draws);  // doubles
 hipError_t launch_glm_terms_prepare(GlmTerms* t, int n_draws, double* uimg, hipStream_t stream);
 hipError_t launch_glm_terms(const GlmLaunch& g, const GlmTerms& t, hipStream_t stream, char* route, int cap);
+// ... the leave-one-out predictive moments and PIT of the model (pla_glm_predict.h): the generator's launch g (out, pitch and
+// replaced unused) contracted against the log weights of its rows -- (n_rows, n_draws), row pitch lw_pitch, unit draw stride.
+// work: glm_predict_workspace(n_rows, n_draws) doubles of this pass alone; mean / m2 / pit_le / pit_lt [n_rows], each may be null;
+// skipped: the rows whose count lies outside [0, kGlmPredictMaxCount], added to (never zeroed here; may be null).
+constexpr int kGlmPredictSeg = 16;          // tiles of 16 draws per segment of the summation rule
+constexpr int kGlmPredictMaxCount = 4096;   // the largest count whose distribution function is walked
+struct GlmPredictLaunch {
+  const double* lw;
+  int64_t lw_pitch;
+  double* work;
+  double *mean, *m2, *pit_le, *pit_lt;
+  unsigned long long* skipped;
+};
+int64_t glm_predict_workspace(int64_t n_rows, int n_draws);
+hipError_t launch_glm_predict(const GlmLaunch& g, const GlmPredictLaunch& q, hipStream_t stream, char* route, int cap);
 // leave-future-out CV (pla_lfo.h).  launch_lfo_ratios: the log ratios of one block of n_rows steps -- whole chunks of
 // lfo_chunk_rows() steps unless it is the last block -- as a contiguous (n_rows, n_draws) f64 matrix; `in` is the row of the block's
 // first step (draws contiguous), rows j < n_load of the block are read (NaN -> -1e10, counted in `replaced`, may be null); carry:

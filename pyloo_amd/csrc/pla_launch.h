@@ -1,6 +1,6 @@
 // Host-side pieces shared by the translation units of libpyloo_amd.so (internal).  The kernels are compiled as several
 // units in parallel (pyloo_amd/build.py): pla_k_general.hip (general kernel, reductions, dispatcher), pla_k_wave_f64/f32.hip,
-// pla_k_chunked_f64/f32.hip, pla_k_fit.hip, pla_k_waic.hip, pla_k_col.hip, pla_k_eloo.hip, pla_k_group.hip, pla_k_compare.hip, pla_k_nonfactor.hip, pla_k_draws.hip, pla_k_kfold.hip, pla_k_mm.hip, pla_k_mixis.hip, pla_k_pit.hip, pla_k_lfo.hip, pla_k_lfo_bw.hip, pla_k_ess.hip, pla_k_diag.hip, pla_k_influence.hip, pla_k_glm.hip, pla_k_glm_terms.hip, pla_k_glm_marginal.hip, pla_k_glm_families.hip, pla_k_glm_terms_families.hip; each launches the kernels it defines.  The C ABI behind them is split the same way: pla_capi.h and the units pla_capi_<family>.hip.
+// pla_k_chunked_f64/f32.hip, pla_k_fit.hip, pla_k_waic.hip, pla_k_col.hip, pla_k_eloo.hip, pla_k_group.hip, pla_k_compare.hip, pla_k_nonfactor.hip, pla_k_draws.hip, pla_k_kfold.hip, pla_k_mm.hip, pla_k_mixis.hip, pla_k_pit.hip, pla_k_lfo.hip, pla_k_lfo_bw.hip, pla_k_ess.hip, pla_k_diag.hip, pla_k_influence.hip, pla_k_glm.hip, pla_k_glm_terms.hip, pla_k_glm_marginal.hip, pla_k_glm_families.hip, pla_k_glm_terms_families.hip, pla_k_glm_predict.hip, pla_k_glm_predict_families.hip; each launches the kernels it defines.  The C ABI behind them is split the same way: pla_capi.h and the units pla_capi_<family>.hip.
 #pragma once
 
 #include <cstdlib>
@@ -75,9 +75,10 @@ constexpr int kSyncQueue = 0, kSyncTake = 16, kSyncGaveUp = 32, kSyncDone = 48;
 // [kCounterBlockTotal] the running total [1] summed over the blocks of a pla_psis_loo_draws call (every block's pass zeroes [1])
 // [kCounterPitReplaced] the NaN entries a host call of pla_loo_pit / pla_loo_diag replaced; [kCounterLfoReplaced], [kCounterLfoFirstHigh] the same
 // and the first step above the threshold of a host call of pla_lfo / pla_lfo_ratios; [kCounterEssInvalid] the invalid rows of a host
-// call of pla_relative_eff; [kCounterGlmReplaced] the NaN entries a host call of pla_glm replaced
+// call of pla_relative_eff; [kCounterGlmReplaced] the NaN entries a host call of pla_glm replaced; [kCounterGlmPitSkipped] the rows beyond the count cap of a
+// pla_glm_predict call that hands no counter of its own
 constexpr int kCountersPerCall = 16, kCounterGaveUp = 16, kCounterBlockTotal = 17, kCounterPitReplaced = 18, kCounterLfoReplaced = 19,
-              kCounterLfoFirstHigh = 20, kCounterEssInvalid = 21, kCounterGlmReplaced = 22, kCountersTotal = 32;
+              kCounterLfoFirstHigh = 20, kCounterEssInvalid = 21, kCounterGlmReplaced = 22, kCounterGlmPitSkipped = 23, kCountersTotal = 32;
 
 // wave-per-observation kernels (pla_wave.h, pla_chunked.h, pla_is.h): one launcher per input dtype, each in a unit of its own
 int64_t wave_grid(int64_t n_obs, int waves);

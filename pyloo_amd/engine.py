@@ -1046,6 +1046,48 @@ class Engine:
         """Members per segment of the summation rule of ``pla_glm_marginal`` (``pla_glm_marginal_segment``)."""
         return load_library().pla_glm_marginal_segment()
 
+    def glm_predict(self, X, beta, family, y=None, offset=None, trials=None, obs_const=None, draw_scale=None, draw_const=None, rows=None,
+                    tail_count=0, method="psis", log_weights=None, pit=True):
+        """The leave-one-out predictive moments and PIT of a generalised linear model from its design matrix, the draws and the
+        family, every argument as :meth:`glm` takes it (``pla_glm_predict``) -> ``dict(mean, m2, pit_le, pit_lt, diag, elpd_i,
+        n_replaced, n_pit_skipped)``, one entry per row of the call.  ``log_weights=None``: the weights are PSIS / SIS / TIS of the
+        model's own log-likelihood, generated and consumed block by block; ``diag`` is their Pareto k (ESS for SIS / TIS).
+        ``log_weights`` (m, n_draws), of any normalisation with unit stride along the draws: used as they are, ``diag`` and
+        ``elpd_i`` are None.  ``pit=False`` (always for ``"gamma"``): the two PIT values are None and nothing is walked for them."""
+        if family == "linpred":
+            raise ValueError("glm_predict needs a likelihood, not family='linpred'")
+        sp, args, _, keep, m, s = self._glm_block(X, beta, family, y, offset, trials, obs_const, draw_scale, draw_const, rows, "loo",
+                                                  tail_count, method, 1.0, 0.7, None)
+        loglik = log_weights is None
+        pred = _capi.GlmPredictArgs(kind=_capi.PLA_PIT_LOGLIK if loglik else _capi.PLA_PIT_LOG_WEIGHTS)
+        p = sp.ptr
+        if not loglik:
+            lw = sp.f64(log_weights)
+            if lw.ndim != 2 or tuple(lw.shape) != (m, s):
+                raise ValueError(f"log_weights must be (rows of the call, n_draws) = ({m}, {s}), got {tuple(lw.shape)}")
+            lw, ls = sp.dense(lw)
+            if s > 1 and int(ls[1]) != 1:
+                lw = lw.contiguous() if sp.device is not None else np.ascontiguousarray(lw)
+                ls = (s, 1)
+            keep.append(lw)
+            pred.log_weights, pred.lw_stride_obs, pred.lw_stride_draw = p(lw), max(int(ls[0]), s), 1
+        want_pit = pit and family != "gamma"
+        out = {"mean": sp.new(m), "m2": sp.new(m), "pit_le": sp.new(m) if want_pit else None, "pit_lt": sp.new(m) if want_pit else None,
+               "diag": sp.new(m) if loglik else None, "elpd_i": sp.new(m) if loglik else None, "n_replaced": sp.counter(),
+               "n_pit_skipped": sp.counter()}
+        for k, v in out.items():
+            setattr(pred, k, p(v))
+        pred.glm = args
+        check(self._lib.pla_glm_predict(C.byref(pred)))
+        del keep
+        out["n_replaced"], out["n_pit_skipped"] = sp.read(out["n_replaced"]), sp.read(out["n_pit_skipped"])
+        return out
+
+    @staticmethod
+    def glm_predict_segment():
+        """Tiles of 16 draws per segment of the summation rule of ``pla_glm_predict`` (``pla_glm_predict_segment``)."""
+        return load_library().pla_glm_predict_segment()
+
     # ------------------------------------------------------------------ leave-future-out CV
     def lfo_ratios(self, ll, first, n_steps):
         """Log ratios of leave-future-out CV (``pla_lfo_ratios``): ``dict(ratios, n_replaced)`` with ``ratios[j, s]`` the sum of rows
