@@ -151,6 +151,15 @@ def weighted(lw, terms):
         return [(np.where(e == 0.0, 0.0, e * np.asarray(t, dtype=np.longdouble)).sum(axis=1) / se).astype(np.float64) for t in terms]
 
 
+def weighted_bound(lw, term):
+    """The bound on a weighted sum of ``term`` (n, S) whose entries are good to ``1e-10 max(1, |term|)`` each (device lgamma / erfcx
+    against scipy's): ``W(1e-10 max(1, |term|)) + (S + 4) 2^-53 W(|term|)`` with ``W`` the weighted mean of ``weighted`` in long
+    double -- a convex combination of the per-element bound, plus the standard bound of a sum of S products and one division."""
+    t = np.abs(np.asarray(term, dtype=np.float64))
+    per_element, magnitude = weighted(lw, [1e-10 * np.maximum(1.0, t), t])
+    return per_element + (t.shape[1] + 4) * 2.0 ** -53 * magnitude
+
+
 def one_hot(n, S, s0):
     lw = np.full((n, S), -np.inf)
     lw[:, s0] = 0.0
